@@ -23,6 +23,9 @@ Extra objects in the line:
                  buckets launched during backward, whether the robust GEMM schedule engaged.
 --torch-ddp / --torch-adamw select the UNCHANGED caller's path (train.py:173-174, utils/train_utils.py:598-608: torch DDP with
 find_unused_parameters, clip_grad_norm_, torch.optim.AdamW) at any N, N = 1 included (a one-rank RCCL group).
+--dump-outputs DIR writes what the last timed step computed as .npy files (dump_outputs), so that two builds can be compared output
+for output: with the same arguments the model, the batch, the dropout / DiT noise streams and (a committed plan replayed) the GEMM
+configurations are the same from run to run.
 """
 import argparse
 import json
@@ -31,6 +34,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -425,6 +429,48 @@ def launch_selftest(rank, world, args):
         dist.destroy_process_group()
 
 
+DUMP_PER_TENSOR = 4096
+
+
+def committed_gemm_plan():
+    """the newest round's committed GEMM plan (profiles/rNN_gemm_plan.json, written by `bench.py --save-plan`), or None"""
+    import glob
+    cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_gemm_plan.json")))
+    return cands[-1] if cands else None
+
+
+def dump_outputs(out_dir, total, parts, named_params, grad_of):
+    """--dump-outputs: what the timed path handed its caller in its last step, rank 0, right after the timed region (before any
+    diagnostic leg steps the model again):
+      loss.npy, loss_<part>.npy : the total loss and each term of the loss block (float64, shape (1,));
+      params.npy, grads.npy     : for every trainable parameter in named_parameters() order, the same fixed sample (numpy
+                                  default_rng(0), at most DUMP_PER_TENSOR elements per tensor, ascending) of the parameter after the
+                                  optimizer step and of the gradient its storage holds (the reducer's bucket, or p.grad; zeros for a
+                                  parameter without one), float32, concatenated -- ~11 MB for the default workload;
+      param_sizes.npy           : how many sampled elements each parameter contributed (float64), to split the two above."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    save("loss", np.array([float(total.detach())], dtype=np.float64))
+    for k, v in parts.items():
+        if torch.is_tensor(v):
+            save(f"loss_{k}", np.array([float(v.detach())], dtype=np.float64))
+    rng = np.random.default_rng(0)
+    ps, gs, sizes = [], [], []
+    for _, p in named_params:
+        n = p.numel()
+        idx = np.arange(n) if n <= DUMP_PER_TENSOR else np.sort(rng.choice(n, DUMP_PER_TENSOR, replace=False))
+        idx = torch.from_numpy(idx).to(p.device)
+        ps.append(p.detach().reshape(-1)[idx].float().cpu())
+        g = grad_of(p)
+        gs.append(torch.zeros(len(idx)) if g is None else g.detach().reshape(-1)[idx].float().cpu())
+        sizes.append(len(idx))
+    save("params", torch.cat(ps).numpy())
+    save("grads", torch.cat(gs).numpy())
+    save("param_sizes", np.array(sizes, dtype=np.float64))
+
+
 def require_finite_loss(loss_val):
     """A model whose parameters have gone non-finite runs FASTER on this chip (round 6, measured: 139 -> 124 ms per step once every
     operand is NaN -- the matrix pipe toggles less and the clocks rise), so such a run must never print a throughput line."""
@@ -475,10 +521,17 @@ def main():
                          "region; rank 0, N = 1 only; ~40 s)")
     ap.add_argument("--launch-selftest", action="store_true",
                     help="CPU-only check of the N > 1 launch path (self-spawn, rendezvous, max over ranks, JSON line); no model")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (loss, loss terms, a fixed sample of the updated "
+                         "parameters and of their gradients) as DIR/<name>.npy (rank 0).  Without --plan / $DVLA_GEMM_PLAN the newest "
+                         "committed plan (profiles/rNN_gemm_plan.json) is replayed: the tuner's timing-dependent choices round differently "
+                         "from run to run, and the training steps amplify that")
     ap.add_argument("--torch-ddp", action="store_true", help="use torch DDP instead of dreamvla_amd.ddp.GradBucketReducer")
     ap.add_argument("--torch-adamw", action="store_true",
                     help="clip_grad_norm_ + torch.optim.AdamW(fused) instead of dreamvla_amd.optim.FlatAdamW (HIP, flat buffers)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch.distributed as dist
     rank = int(os.environ.get("RANK", "0"))
@@ -509,6 +562,7 @@ def main():
     from dreamvla_amd.synthetic import synthetic_batch
 
     torch.manual_seed(1234 + rank)
+    np.random.seed(1234 + rank)      # the pretrain phase draws its per-step mask columns from numpy's global stream
     ops.set_seed_salt(rank)
     BF = torch.bfloat16
     S, B = args.seq, args.batch
@@ -548,15 +602,14 @@ def main():
 
     def forward_loss():
         out = ddp_model(*inputs, action=batch["actions"][:, :S], action_label=lab, mode="train")
-        total, _ = losses.calvin_losses(out, batch, sequence_length=S, use_dit_head=cfg["use_dit_head"], label_action=lab)
-        return total
+        return losses.calvin_losses(out, batch, sequence_length=S, use_dit_head=cfg["use_dit_head"], label_action=lab)
 
     def step():
         if reducer is not None:
             reducer.zero_grad()
         else:
             opt.zero_grad(set_to_none=False)
-        total = forward_loss()
+        total, parts = forward_loss()
         total.backward()
         if reducer is not None:
             reducer.finish()
@@ -565,7 +618,7 @@ def main():
         else:
             torch.nn.utils.clip_grad_norm_(model.parameters() if args.torch_ddp else params, 0.1)   # utils/train_utils.py:600
             opt.step()
-        return total
+        return total, parts
 
     def sync():
         if world > 1:
@@ -574,6 +627,8 @@ def main():
 
     from dreamvla_amd.ops import GemmTuner
     plan = args.plan or os.environ.get("DVLA_GEMM_PLAN")
+    if not plan and args.dump_outputs:
+        plan = committed_gemm_plan()
     if plan and os.path.exists(plan):
         GemmTuner.load_plan(plan)
     elif GemmTuner.enabled:
@@ -587,7 +642,7 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        last = step()
+        last, last_parts = step()
     sync()
     dt = time.perf_counter() - t0
     if world > 1:
@@ -610,6 +665,9 @@ def main():
                          "predicted_weak_scaling_efficiency_8gpu": "0.97-0.98 (DESIGN.md section 8)"})
     ms_per_step = dt / args.steps * 1e3
     value = B * world * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, last_parts, [(n, p) for n, p in model.named_parameters() if p.requires_grad],
+                     reducer.grad_of if reducer is not None else (lambda p: p.grad))
     loss_val = require_finite_loss(float(last.detach()))
 
     if args.torch_profile and rank == 0:
@@ -736,7 +794,7 @@ def main():
             "metric": "train samples/sec (CALVIN ABC->D, seq_len=7)", "value": value, "unit": "samples/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
             "fwd_ms_per_step": fwd_ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16", "data": "synthetic",
+            "dtype": "bf16", "data": "synthetic", "gemm_plan": os.path.relpath(plan, ROOT) if plan and os.path.exists(plan) else None,
             "config": {"workload": f"DreamVLA CALVIN {args.phase} step, head set {args.heads} "
                                    f"({'+'.join(k for k in HEAD_SETS[args.heads] if HEAD_SETS[args.heads][k])}), "
                                    f"B={B}/GPU, S={S}, window {S + 3}, 2x224^2 views, 77 text tokens, hidden 1024 / "

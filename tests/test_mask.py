@@ -1,11 +1,15 @@
 """Host logic (CPU): attention-mask generator bit-exactness vs the reference + the kernel's mask tables."""
 
+import functools
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
 
 from dreamvla_amd.dreamvla_model import generate_attention_mask
-from oracle import ref_loader
 
 COMBOS = [dict(K=K, num_A=36, num_B=nq + aps, atten_goal=ag, atten_goal_state=ags, atten_only_obs=aoo,
                attn_robot_proprio_state=arps, mask_l_obs_ratio=ml, num_obs_token=nq, action_pred_steps=aps)
@@ -16,19 +20,24 @@ COMBOS = [dict(K=K, num_A=36, num_B=nq + aps, atten_goal=ag, atten_goal_state=ag
               (6, 18, 0, 0, False, False, False, 0.0), (4, 36, 1, 2, True, False, True, 0.0)]]
 
 
-@pytest.mark.skipif(not ref_loader.available(), reason="reference tree not present")
+@functools.lru_cache(maxsize=None)
+def _fingerprints():
+    with open(os.path.join(os.path.dirname(__file__), "golden", "reference_fingerprints.json")) as f:
+        return json.load(f)
+
+
 @pytest.mark.parametrize("kw", COMBOS)
 def test_mask_bit_exact_vs_reference(kw):
-    ref = ref_loader.ref_module("models.dreamvla_model").generate_attention_mask
-    np.random.seed(123)
-    a = ref(**kw)
+    """the REAL reference's mask for the same flags and numpy seed, fingerprinted bit for bit (shape, dtype, SHA-256 of the bytes)
+    by oracle/make_golden_fingerprints.py into tests/golden/reference_fingerprints.json"""
+    ref = next(f for f in _fingerprints()["masks"] if f["kw"] == kw)
     np.random.seed(123)
     b = generate_attention_mask(**kw)
-    assert a.shape == b.shape and torch.equal(a, b)
+    assert list(b.shape) == ref["shape"] and str(b.dtype) == ref["dtype"]
+    assert hashlib.sha256(b.contiguous().numpy().tobytes()).hexdigest() == ref["sha256"]
 
 
 def test_mask_golden():
-    import os
     g = torch.load(os.path.join(os.path.dirname(__file__), "golden", "masks.pt"))
     for kw, packed in zip(COMBOS, g["packed"]):
         np.random.seed(123)
