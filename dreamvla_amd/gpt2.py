@@ -48,9 +48,9 @@ class GPT2Attention(nn.Module):
         self.embed_dim = config.hidden_size
         self.num_heads = config.num_attention_heads
         self.head_dim = self.embed_dim // self.num_heads
-        if self.head_dim != 64:
-            raise ValueError("HIP attention kernels are specialised for head_dim 64 "
-                             f"(hidden {self.embed_dim} / heads {self.num_heads} = {self.head_dim})")
+        if self.head_dim * self.num_heads != self.embed_dim or not (self.head_dim == 64 or ops.attn_hd_supported(self.head_dim)):
+            raise ValueError("HIP attention kernels take head_dim 64 or a multiple of 8 from 8 to 128 "
+                             f"(hidden {self.embed_dim} / heads {self.num_heads} = {self.embed_dim / self.num_heads:g})")
         self.layer_idx = layer_idx
         self.c_attn = Conv1D(3 * self.embed_dim, self.embed_dim)
         self.c_proj = Conv1D(self.embed_dim, self.embed_dim)
@@ -59,7 +59,7 @@ class GPT2Attention(nn.Module):
     def forward(self, hidden_states, mask_tables=None, residual=None):
         qkv = self.c_attn(hidden_states)
         o = ops.self_attention(qkv, self.num_heads, scale=1.0 / math.sqrt(self.head_dim), mask_tables=mask_tables,
-                               dropout_p=self.attn_pdrop if self.training else 0.0)
+                               dropout_p=self.attn_pdrop if self.training else 0.0, head_dim=self.head_dim)
         return self.c_proj(o, residual=residual, dropout_p=self.resid_pdrop if self.training else 0.0)
 
 

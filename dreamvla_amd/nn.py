@@ -72,8 +72,10 @@ class Mlp(nn.Module):
 
 class Attention(nn.Module):
     """timm Attention: fused qkv Linear -> (B,N,3,h,d) -> SDPA (scale d^-0.5) -> proj.  head_dim 64 runs on the MFMA kernels
-    (csrc/attention.hip); any other head_dim <= 128 (DiT-S: 96) on the short-sequence kernel (csrc/attention_small.hip,
-    sequences of at most 64 tokens, no mask) -- ops.self_attention raises for anything else."""
+    (csrc/attention.hip).  Any other head_dim that is a multiple of 8 up to 128 runs on the short-sequence kernel
+    (csrc/attention_small.hip: at most 64 tokens, no mask -- DiT-S, 96) or else on the head-width-generic kernels
+    (csrc/attention_hd.hip: any length, masks, dropout -- the 16-head dream-head decoders at hidden_dim != 1024, e.g. 24 at
+    384).  ops.self_attention raises for any other head_dim."""
 
     def __init__(self, dim, num_heads=8, qkv_bias=False):
         super().__init__()
@@ -122,7 +124,7 @@ class Block(nn.Module):
         gradient over the batch before the (tiny) backward GEMMs.   prefix (n_seq, n_q, D), suffix (n_suffix, D)."""
         x = ops.concat_shared_suffix(prefix, suffix)
         qkv = ops.concat_shared_suffix(self.attn.qkv(self.norm1(prefix)), self.attn.qkv(self.norm1(suffix)))
-        o = ops.self_attention(qkv, self.attn.num_heads, scale=self.attn.scale)
+        o = ops.self_attention(qkv, self.attn.num_heads, scale=self.attn.scale, head_dim=self.attn.head_dim)
         x = self.attn.proj(o, residual=x)
         r, n = self.norm2.fork(x)
         return self.mlp(n, residual=r)

@@ -820,13 +820,13 @@ def mask_tables_for(mask):
     return mt
 
 
-def _attn_params(q, k, v, o, H, Lq, scale, mt, dropout_p, seed, lse):
+def _attn_params(q, k, v, o, H, Lq, scale, mt, dropout_p, seed, lse, head_dim=64):
     p = AttnParams()
     B = q.shape[0]
     p.q, p.k, p.v, p.o = q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr()
     for name, t in (("q", q), ("k", k), ("v", v), ("o", o)):
-        if t.stride(3) != 1 or t.shape[3] != 64:
-            raise ValueError("attention expects (B, L, H, 64) views with unit inner stride")
+        if t.stride(3) != 1 or t.shape[3] != head_dim:
+            raise ValueError(f"attention expects (B, L, H, {head_dim}) views with unit inner stride")
         setattr(p, name + "_stride_b", t.stride(0))
         setattr(p, name + "_stride_t", t.stride(1))
         setattr(p, name + "_stride_h", t.stride(2))
@@ -845,26 +845,35 @@ def _attn_params(q, k, v, o, H, Lq, scale, mt, dropout_p, seed, lse):
     return p
 
 
-def attn_fwd_raw(q, k, v, *, scale, mask_tables=None, dropout_p=0.0, seed=(0, 0), want_lse=True):
-    """q: (B, Lq, H, 64), k/v: (B, Lk, H, 64) strided bf16 views.  Returns o (B, Lq, H, 64) contiguous, lse."""
+def attn_hd_supported(head_dim):
+    """head widths of dvla_attn_hd_fwd / _bwd (every width but 64, which has its own kernels): multiples of 8 up to 128"""
+    return 8 <= head_dim <= 128 and head_dim % 8 == 0 and head_dim != 64
+
+
+def attn_fwd_raw(q, k, v, *, scale, mask_tables=None, dropout_p=0.0, seed=(0, 0), want_lse=True, head_dim=64):
+    """q: (B, Lq, H, D), k/v: (B, Lk, H, D) strided bf16 views.  Returns o (B, Lq, H, D) contiguous, lse.
+    D = 64: dvla_attn_fwd; any other D (attn_hd_supported): dvla_attn_hd_fwd, same masks / dropout / lse."""
     lib = _lib.load()
     for n, t in (("q", q), ("k", k), ("v", v)):
         _req(t, "attention." + n)
     B, Lq, H, _ = q.shape
-    o = torch.empty((B, Lq, H, 64), dtype=BF16, device=q.device)
+    o = torch.empty((B, Lq, H, head_dim), dtype=BF16, device=q.device)
     lse = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device) if want_lse else None
-    p = _attn_params(q, k, v, o, H, Lq, scale, mask_tables, dropout_p, seed, lse)
-    check(lib.dvla_attn_fwd(C.byref(p), _stream()), "dvla_attn_fwd")
+    p = _attn_params(q, k, v, o, H, Lq, scale, mask_tables, dropout_p, seed, lse, head_dim)
+    if head_dim == 64:
+        check(lib.dvla_attn_fwd(C.byref(p), _stream()), "dvla_attn_fwd")
+    else:
+        check(lib.dvla_attn_hd_fwd(C.byref(p), int(head_dim), _stream()), "dvla_attn_hd_fwd")
     return o, lse
 
 
-def attn_bwd_raw(q, k, v, o, lse, dout, dq, dk, dv, *, scale, mask_tables=None, dropout_p=0.0, seed=(0, 0)):
+def attn_bwd_raw(q, k, v, o, lse, dout, dq, dk, dv, *, scale, mask_tables=None, dropout_p=0.0, seed=(0, 0), head_dim=64):
     """dk/dv rows that mask_tables.key_index does not name are NOT written: pass zero-filled buffers then."""
     lib = _lib.load()
     B, Lq, H, _ = q.shape
     if dout.stride(3) != 1:
         dout = dout.contiguous()
-    p = _attn_params(q, k, v, o, H, Lq, scale, mask_tables, dropout_p, seed, lse)
+    p = _attn_params(q, k, v, o, H, Lq, scale, mask_tables, dropout_p, seed, lse, head_dim)
     delta = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
     p.dout = dout.data_ptr()
     p.do_stride_b, p.do_stride_t, p.do_stride_h = dout.stride(0), dout.stride(1), dout.stride(2)
@@ -874,7 +883,10 @@ def attn_bwd_raw(q, k, v, o, lse, dout, dq, dk, dv, *, scale, mask_tables=None, 
         setattr(p, name + "_stride_b", t.stride(0))
         setattr(p, name + "_stride_t", t.stride(1))
         setattr(p, name + "_stride_h", t.stride(2))
-    check(lib.dvla_attn_bwd(C.byref(p), _stream()), "dvla_attn_bwd")
+    if head_dim == 64:
+        check(lib.dvla_attn_bwd(C.byref(p), _stream()), "dvla_attn_bwd")
+    else:
+        check(lib.dvla_attn_hd_bwd(C.byref(p), int(head_dim), _stream()), "dvla_attn_hd_bwd")
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -1497,6 +1509,55 @@ class _SelfAttentionSmall(torch.autograd.Function):
         return dqkv, None, None, None
 
 
+class _SelfAttentionHD(torch.autograd.Function):
+    """Packed self-attention with head_dim D != 64 (attn_hd_supported) at any length, with masks and dropout
+    (dvla_attn_hd_fwd / _bwd): the trunk of a model whose hidden_dim / transformer_heads is not 64 and the 16-head dream-head
+    decoders of any hidden_dim != 1024.  qkv (B, L, 3*H*D) -> (B, L, H*D); same tables, seeds and zero-fill rules as
+    _SelfAttention."""
+
+    @staticmethod
+    def forward(ctx, qkv, H, D, scale, mask_tables, dropout_p):
+        _req(qkv, "attention.qkv")
+        B, L, W = qkv.shape
+        if W != 3 * H * D:
+            raise ValueError("attention: qkv width must be 3 * heads * head_dim")
+        if not qkv.is_contiguous():
+            qkv = qkv.contiguous()
+        v5 = qkv.view(B, L, 3, H, D)
+        need_grad = any(ctx.needs_input_grad)
+        seed = next_seed() if dropout_p > 0 else (0, 0)
+        o, lse = attn_fwd_raw(v5[:, :, 0], v5[:, :, 1], v5[:, :, 2], scale=scale, mask_tables=mask_tables,
+                              dropout_p=dropout_p, seed=seed, want_lse=need_grad, head_dim=D)
+        ctx.H, ctx.D, ctx.scale, ctx.dropout_p, ctx.seed, ctx.mt = H, D, scale, dropout_p, seed, mask_tables
+        if need_grad:
+            ctx.save_for_backward(qkv, o, lse)
+        return o.view(B, L, H * D)
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, o, lse = ctx.saved_tensors
+        B, L, _ = qkv.shape
+        H, D, mt = ctx.H, ctx.D, ctx.mt
+        v5 = qkv.view(B, L, 3, H, D)
+        dead = getattr(mt, "dead_keys", None) if mt is not None else None
+        if mt is not None and mt.key_index is not None and dead is None:
+            dqkv = torch.zeros_like(qkv)
+        else:
+            dqkv = torch.empty_like(qkv)
+            if dead is not None and dead.numel():
+                dqkv.view(B, L, 3, H * D)[:, :, 1:].index_fill_(1, dead, 0)
+        d5 = dqkv.view(B, L, 3, H, D)
+        do = _req(dout, "attention.grad_output").contiguous().view(B, L, H, D)
+        attn_bwd_raw(v5[:, :, 0], v5[:, :, 1], v5[:, :, 2], o, lse, do, d5[:, :, 0], d5[:, :, 1], d5[:, :, 2],
+                     scale=ctx.scale, mask_tables=mt, dropout_p=ctx.dropout_p, seed=ctx.seed, head_dim=D)
+        return dqkv, None, None, None, None, None
+
+
+def _small_attention_fits(B, L, D):
+    """the shapes _SelfAttentionSmall takes (its kernel's limits, include/dvla.h)"""
+    return L <= 64 and D <= 128 and D % 8 == 0 and (4 * L * (D + 1) + 2 * L * (L + 1)) * 4 <= 160 * 1024 and B <= 65535
+
+
 _PACK_TABLES = {}
 
 
@@ -1513,7 +1574,9 @@ def _packed_block_diagonal(G, L, device):
 
 
 def self_attention(qkv, num_heads, *, scale=None, mask_tables=None, dropout_p=0.0, head_dim=64):
-    """qkv (B, L, 3 * H * 64) -> (B, L, H * 64).  head_dim != 64: the short-sequence kernel (_SelfAttentionSmall).
+    """qkv (B, L, 3 * H * D) -> (B, L, H * D).  head_dim 64: the kernels below.  Any other head_dim: short sequences without
+    mask or dropout take the short-sequence kernel (_SelfAttentionSmall: the DiT-S head), everything else the head-width-generic
+    kernels (_SelfAttentionHD: multiples of 8 up to 128).
     Very short sequences (the DiT action head: L = 6, B = 1792) are PACKED: G consecutive sequences are handed to the
     kernels as one sequence of G * L tokens under a block-diagonal mask (a view -- the batch is contiguous -- plus a cached
     table): the kernels work on 32 x 32 score tiles and 128-query workgroups, so one 6 x 6 problem per workgroup used
@@ -1523,9 +1586,12 @@ def self_attention(qkv, num_heads, *, scale=None, mask_tables=None, dropout_p=0.
     qkv = to_compute(qkv)
     B, L = qkv.shape[0], qkv.shape[1]
     if head_dim != 64:
-        if mask_tables is not None or dropout_p > 0.0:
-            raise _lib.DvlaError(f"attention with head_dim {head_dim}: masks / dropout need the head_dim-64 kernels")
-        return _SelfAttentionSmall.apply(qkv, int(num_heads), int(head_dim), float(scale))
+        if mask_tables is None and dropout_p == 0.0 and _small_attention_fits(B, L, head_dim):
+            return _SelfAttentionSmall.apply(qkv, int(num_heads), int(head_dim), float(scale))
+        if not attn_hd_supported(head_dim):
+            raise _lib.DvlaError(f"attention with head_dim {head_dim}: supported head widths are 64 and the multiples of 8 "
+                                 f"from 8 to 128")
+        return _SelfAttentionHD.apply(qkv, int(num_heads), int(head_dim), float(scale), mask_tables, float(dropout_p))
     if mask_tables is None and dropout_p == 0.0 and 1 < L <= 16 and B >= 64 and qkv.is_contiguous():
         G = 128 // L
         while G > 1 and B % G != 0:

@@ -167,8 +167,9 @@ int dvla_layernorm_bwd_rows(const void* dy, const void* x, const void* gamma, in
                             int32_t grp, int32_t gstride, int32_t goff, int32_t map_output, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
- * Fused multi-head attention, head_dim = 64 (every attention in DreamVLA: ViT 768/12, trunk 1024/16,
- * dream-head decoders 1024/16, DiT 768/12, perceiver dim_head 64, CLIP text 512/8).
+ * Fused multi-head attention, head_dim = 64 (ViT 768/12, trunk 1024/16, dream-head decoders 1024/16, DiT 768/12,
+ * perceiver dim_head 64, CLIP text 512/8).  Other head widths (models of another hidden_dim or head count, and the
+ * 16-head dream-head decoders of any hidden_dim != 1024) take dvla_attn_hd_fwd / dvla_attn_hd_bwd below.
  *   O[b,i,h,:] = sum_j drop( softmax_j( scale * q[b,i,h,:].k[b,j,h,:] + mask[i,j] ) ) * v[b,j,h,:]
  * q/k/v/o element (b, token, head, d) lives at ptr[b*stride_b + token*stride_t + head*stride_h + d], so
  * the fused (B,N,3,h,d) timm qkv buffer, the GPT-2 c_attn (B,L,3H) buffer and the perceiver q / kv
@@ -218,6 +219,12 @@ int dvla_attn_bwd(const dvla_attn_params* p, void* stream);
  * action_model.py:12-14: 384 / 4 = 96) on 6-token sequences.  Same parameter block; `delta` is not used. */
 int dvla_attn_small_fwd(const dvla_attn_params* p, int32_t head_dim, void* stream);
 int dvla_attn_small_bwd(const dvla_attn_params* p, int32_t head_dim, void* stream);
+/* (additive, ABI 8) The same attention as dvla_attn_fwd / dvla_attn_bwd -- same parameter block, masks, key_index, dropout keep
+ * mask, lse and delta -- for head_dim a multiple of 8 with 8 <= head_dim <= 128 and head_dim != 64 (DVLA_ERR_UNSUPPORTED
+ * otherwise).  The kernels run at head_dim rounded up to a multiple of 32 with the extra d columns zero; columns >= head_dim of
+ * o / dq / dk / dv are not written.  q / k / v / dout (and o in backward) need 16-byte aligned rows, o / dq / dk / dv 8-byte. */
+int dvla_attn_hd_fwd(const dvla_attn_params* p, int32_t head_dim, void* stream);
+int dvla_attn_hd_bwd(const dvla_attn_params* p, int32_t head_dim, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Small HBM-bound helpers (bf16 unless noted).
