@@ -89,6 +89,13 @@ class FrameView(C.Structure):
     _fields_ = [("base", C.c_void_p), ("stride_b", C.c_int64), ("stride_t", C.c_int64), ("T", C.c_int32)]
 
 
+class MaeLossParams(C.Structure):
+    _fields_ = [("pred", C.c_void_p), ("pred_stride_n", C.c_int64), ("pred_stride_r", C.c_int64), ("row0", C.c_int32),
+                ("patch", C.c_int32),
+                ("imgs", C.c_void_p), ("imgs_dtype", C.c_int32), ("norm_pix", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("mask", C.c_void_p), ("N", C.c_int64)]
+
+
 # every symbol include/dvla.h declares: (name, restype, argtypes)
 _P, _I64, _I32, _F, _U32 = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_uint32
 SYMBOLS = {
@@ -138,6 +145,13 @@ SYMBOLS = {
     "dvla_silog_loss_bwd": (C.c_int, [C.POINTER(FrameView), C.POINTER(FrameView), _I64, _F, _P, _P, C.POINTER(FrameView), _P]),
     "dvla_sumsq_partial_len": (C.c_int64, []),
     "dvla_sumsq_bf16": (C.c_int, [_P, _I64, _P, _P, C.c_int32, _P]),
+    "dvla_mae_mask_fwd": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "dvla_mae_mask_bwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "dvla_mae_unshuffle_fwd": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P]),
+    "dvla_mae_unshuffle_bwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _P]),
+    "dvla_mae_loss_partial_len": (C.c_int64, []),
+    "dvla_mae_loss_fwd": (C.c_int, [C.POINTER(MaeLossParams), _P, _P, _P]),
+    "dvla_mae_loss_bwd": (C.c_int, [C.POINTER(MaeLossParams), _P, _P, _P, _P]),
     "dvla_adamw_bf16": (C.c_int, [_P, _P, _P, _P, _I64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I64, _P,
                                   C.c_float, _P]),
 }

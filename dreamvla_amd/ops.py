@@ -1775,3 +1775,186 @@ class _Act(torch.autograd.Function):
 
 def activation(x, act):
     return _Act.apply(to_compute(x), ACT[act] if isinstance(act, str) else int(act))
+
+
+# ---------------------------------------------------------------------------------------------------
+# MAE pretraining (csrc/mae.hip): random masking, the decoder's token un-shuffle, the patch-MSE loss
+# ---------------------------------------------------------------------------------------------------
+MAE_MAX_TOKENS = 1024       # patches per image held in LDS by the masking / un-shuffle kernels
+MAE_MAX_DEC_WIDTH = 2048    # decoder width of the un-shuffle backward (8 columns per thread, 256 threads)
+
+
+def _aligned(t):
+    """t contiguous with a 16-byte aligned base (the 16-byte vector kernels need both)"""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _bf16_row(p, cols, name):
+    """a (.., cols) parameter (bf16 or fp32 master) as a contiguous, aligned bf16 row table; no gradient recorded"""
+    _param_dt(p, name)
+    return _aligned(cast_to(p.detach().reshape(-1, cols), BF16))
+
+
+def _mae_shape_check(N, L, D, len_keep, what, max_d=None):
+    if N > 65535 or L > MAE_MAX_TOKENS or not (0 < len_keep <= L) or D % 8 != 0 or (max_d is not None and D > max_d):
+        raise _lib.DvlaError(f"{what}: unsupported shape (N={N}, L={L}, D={D}, len_keep={len_keep}): the kernels take N <= "
+                             f"65535, L <= {MAE_MAX_TOKENS}, 0 < len_keep <= L and D % 8 == 0" + (f", D <= {max_d}" if max_d else ""))
+
+
+class _MaeMask(torch.autograd.Function):
+    """random_masking + the encoder's cls concat (models/vit_mae.py:157-199) in one launch.  ids_shuffle is the stable ascending
+    order of `noise` per sample (torch.argsort(noise, dim=1, stable=True)); out = [cls_row ; x[n, ids_shuffle[n, :len_keep]]]
+    (no cls row when cls_row is None).  Backward: the kept rows' gradient scattered back to their positions (removed rows zero);
+    the cls row's gradient is the column sum of out-gradient row 0."""
+
+    @staticmethod
+    def forward(ctx, x, cls_row, noise, len_keep):
+        lib = _lib.load()
+        _req(x, "mae_mask.x"); _req(noise, "mae_mask.noise", torch.float32)
+        if x.dim() != 3 or noise.shape != x.shape[:2]:
+            raise ValueError(f"mae_mask: x (N, L, D) and noise (N, L), got {tuple(x.shape)} and {tuple(noise.shape)}")
+        N, L, D = x.shape
+        _mae_shape_check(N, L, D, len_keep, "mae_mask")
+        x = _aligned(x)
+        noise = noise.contiguous()
+        cls = _bf16_row(cls_row, D, "mae_mask.cls_row") if cls_row is not None else None
+        c = 1 if cls is not None else 0
+        out = torch.empty((N, c + len_keep, D), dtype=BF16, device=x.device)
+        ids_restore = torch.empty((N, L), dtype=torch.int64, device=x.device)
+        mask = torch.empty((N, L), dtype=torch.float32, device=x.device)
+        check(lib.dvla_mae_mask_fwd(noise.data_ptr(), x.data_ptr(), _ptr(cls), N, L, D, len_keep, ids_restore.data_ptr(),
+                                    mask.data_ptr(), out.data_ptr(), _stream()), "dvla_mae_mask_fwd")
+        ctx.mark_non_differentiable(mask, ids_restore)
+        ctx.save_for_backward(ids_restore)
+        ctx.c, ctx.len_keep, ctx.shape = c, len_keep, (N, L, D)
+        ctx.cls_dtype = None if cls_row is None else cls_row.dtype
+        ctx.cls_shape = None if cls_row is None else cls_row.shape
+        return out, mask, ids_restore
+
+    @staticmethod
+    def backward(ctx, dout, _dmask, _dids):
+        lib = _lib.load()
+        (ids_restore,) = ctx.saved_tensors
+        N, L, D = ctx.shape
+        dout = _aligned(_req(dout, "mae_mask.grad_output"))
+        dx = dcls = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty((N, L, D), dtype=BF16, device=dout.device)
+            check(lib.dvla_mae_mask_bwd(ids_restore.data_ptr(), dout.data_ptr(), ctx.c, N, L, D, ctx.len_keep, dx.data_ptr(),
+                                        _stream()), "dvla_mae_mask_bwd")
+        if ctx.c and ctx.needs_input_grad[1]:
+            dcls = colsum(dout[:, 0, :], ctx.cls_dtype).view(ctx.cls_shape)
+        return dx, dcls, None, None
+
+
+def mae_random_masking(x, noise, len_keep, cls_row=None):
+    """(x_masked, mask, ids_restore) of MaskedAutoencoderViT.random_masking for the bf16 tokens x (N, L, D) and fp32 noise (N, L);
+    with cls_row (D elements, bf16 or fp32) x_masked is [cls_row ; kept tokens], (N, 1 + len_keep, D)."""
+    return _MaeMask.apply(to_compute(x), cls_row, noise, int(len_keep))
+
+
+class _MaeUnshuffle(torch.autograd.Function):
+    """The MAE decoder's token assembly (models/vit_mae.py:213-219): out[n, 0] = y[n, 0] + pos[0], out[n, 1 + l] = (kept ? y[n, 1 +
+    ids_restore[n, l]] : mask_token) + pos[1 + l], one launch.  Backward: dy gathers the cls row and the kept rows; d mask_token
+    is the fp32 sum over every removed row of every sample (fixed order), written in mask_token's dtype.  pos gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, y, mask_token, ids_restore, pos):
+        lib = _lib.load()
+        _req(y, "mae_unshuffle.y"); _req(ids_restore, "mae_unshuffle.ids_restore", torch.int64)
+        if y.dim() != 3 or ids_restore.dim() != 2 or ids_restore.shape[0] != y.shape[0]:
+            raise ValueError(f"mae_unshuffle: y (N, 1 + len_keep, D) and ids_restore (N, L), got {tuple(y.shape)} and "
+                             f"{tuple(ids_restore.shape)}")
+        if pos.requires_grad:
+            raise ValueError("mae_unshuffle: the position table must not require grad (decoder_pos_embed is fixed)")
+        N, R, D = y.shape
+        L = ids_restore.shape[1]
+        len_keep = R - 1
+        _mae_shape_check(N, L, D, len_keep, "mae_unshuffle", MAE_MAX_DEC_WIDTH)
+        if pos.numel() != (1 + L) * D:
+            raise ValueError(f"mae_unshuffle: position table of {(1 + L) * D} elements expected, got {tuple(pos.shape)}")
+        y = _aligned(y)
+        ids = ids_restore.contiguous()
+        mt = _bf16_row(mask_token, D, "mae_unshuffle.mask_token")
+        pz = _bf16_row(pos, D, "mae_unshuffle.pos")
+        out = torch.empty((N, 1 + L, D), dtype=BF16, device=y.device)
+        check(lib.dvla_mae_unshuffle_fwd(y.data_ptr(), mt.data_ptr(), ids.data_ptr(), pz.data_ptr(), N, L, D, len_keep,
+                                         out.data_ptr(), _stream()), "dvla_mae_unshuffle_fwd")
+        ctx.save_for_backward(ids)
+        ctx.shape, ctx.mt_dtype, ctx.mt_shape = (N, L, D, len_keep), mask_token.dtype, mask_token.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        (ids,) = ctx.saved_tensors
+        N, L, D, len_keep = ctx.shape
+        dout = _aligned(_req(dout, "mae_unshuffle.grad_output"))
+        dy = torch.empty((N, 1 + len_keep, D), dtype=BF16, device=dout.device)
+        dmt = torch.empty(D, dtype=ctx.mt_dtype, device=dout.device)
+        part = torch.empty(4 * N * D, dtype=torch.float32, device=dout.device)     # 4 partial rows per sample
+        check(lib.dvla_mae_unshuffle_bwd(dout.data_ptr(), ids.data_ptr(), N, L, D, len_keep, dy.data_ptr(), dmt.data_ptr(),
+                                         _dt(dmt), part.data_ptr(), _stream()), "dvla_mae_unshuffle_bwd")
+        return dy, (dmt.view(ctx.mt_shape) if ctx.needs_input_grad[1] else None), None, None
+
+
+def mae_unshuffle(y, mask_token, ids_restore, pos):
+    """decoder tokens (N, 1 + L, D) from decoder_embed's output y (N, 1 + len_keep, D), the mask token (D elements), ids_restore
+    (N, L) int64 and the (1 + L, D) position table"""
+    return _MaeUnshuffle.apply(to_compute(y), mask_token, ids_restore, pos)
+
+
+class _MaeLoss(torch.autograd.Function):
+    """MaskedAutoencoderViT.forward_loss fused with patchify (models/vit_mae.py:129-141,234-250): pred (N, R, P) bf16 whose last
+    L = (H / p) (W / p) rows are the patch predictions (R = L, or L + 1 with the decoder's cls row first, which is skipped in
+    place); imgs (N, 3, H, W) fp32 or bf16; mask (N, L) fp32.  fp32 scalar loss; dpred written as bf16 (N, R, P) with the
+    skipped rows zero.  imgs and mask get no gradient."""
+
+    @staticmethod
+    def _params(pred, imgs, mask, patch, norm_pix):
+        N, R, P = pred.shape
+        H, W = imgs.shape[2], imgs.shape[3]
+        L = (H // patch) * (W // patch)
+        return _lib.MaeLossParams(pred.data_ptr(), pred.stride(0), pred.stride(1), R - L, patch, imgs.data_ptr(), _dt(imgs),
+                                  int(bool(norm_pix)), H, W, mask.data_ptr(), N)
+
+    @staticmethod
+    def forward(ctx, pred, imgs, mask, patch, norm_pix):
+        lib = _lib.load()
+        _req(pred, "mae_loss.pred"); _req(imgs, "mae_loss.imgs", None); _req(mask, "mae_loss.mask", torch.float32)
+        if imgs.dtype not in (torch.float32, BF16) or imgs.dim() != 4 or imgs.shape[1] != 3:
+            raise _lib.DvlaError(f"mae_loss: imgs (N, 3, H, W) fp32 or bf16, got {tuple(imgs.shape)} {imgs.dtype}")
+        N, R, P = pred.shape
+        H, W = imgs.shape[2], imgs.shape[3]
+        if not (1 <= patch <= 16) or H % patch or W % patch or P != 3 * patch * patch:
+            raise _lib.DvlaError(f"mae_loss: unsupported patch {patch} for images {H}x{W} and predictions of {P} (p <= 16, "
+                                 f"H and W multiples of p, P = 3 p^2)")
+        L = (H // patch) * (W // patch)
+        if imgs.shape[0] != N or tuple(mask.shape) != (N, L) or R - L not in (0, 1):
+            raise ValueError(f"mae_loss: pred {tuple(pred.shape)}, imgs {tuple(imgs.shape)}, mask {tuple(mask.shape)} disagree")
+        if pred.stride(2) != 1:
+            pred = pred.contiguous()
+        imgs, mask = imgs.contiguous(), mask.contiguous()
+        out2 = torch.empty(2, dtype=torch.float32, device=pred.device)
+        part = torch.empty(lib.dvla_mae_loss_partial_len(), dtype=torch.float32, device=pred.device)
+        prm = _MaeLoss._params(pred, imgs, mask, patch, norm_pix)
+        check(lib.dvla_mae_loss_fwd(C.byref(prm), out2.data_ptr(), part.data_ptr(), _stream()), "dvla_mae_loss_fwd")
+        ctx.save_for_backward(pred, imgs, mask, out2)
+        ctx.patch, ctx.norm_pix = patch, norm_pix
+        return out2[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        pred, imgs, mask, out2 = ctx.saved_tensors
+        g = g.detach().float().reshape(1).contiguous()
+        dpred = torch.empty(pred.shape, dtype=BF16, device=pred.device)
+        prm = _MaeLoss._params(pred, imgs, mask, ctx.patch, ctx.norm_pix)
+        check(lib.dvla_mae_loss_bwd(C.byref(prm), out2.data_ptr(), g.data_ptr(), dpred.data_ptr(), _stream()), "dvla_mae_loss_bwd")
+        return dpred, None, None, None, None
+
+
+def mae_loss(pred, imgs, mask, patch, norm_pix=False):
+    """sum(mask * mean_P((pred - patchify(imgs))^2)) / sum(mask) (norm_pix: per-patch normalised target)"""
+    return _MaeLoss.apply(to_compute(pred), imgs, mask, int(patch), bool(norm_pix))

@@ -1,14 +1,19 @@
-"""MAE ViT-B/16 encoder on the HIP kernels -- host-side mirror of /root/reference/models/vit_mae.py.
+"""MaskedAutoencoderViT on the HIP kernels -- host-side mirror of the reference's models/vit_mae.py.
 
-Same constructor, parameter names and shapes as the reference `MaskedAutoencoderViT` (including the MAE
-decoder half, which DreamVLA never calls but whose tensors are part of the checkpoint / state_dict surface,
-vit_mae.py:82-97).  Only `forward_encoder` is on the hot path (dreamvla_model.py:672-673).
+Same constructor, parameter names and shapes as the reference `MaskedAutoencoderViT`, and the same methods: patchify /
+unpatchify, random_masking, forward_encoder, forward_decoder, forward_loss and forward (MAE pretraining).  DreamVLA calls only
+`forward_encoder(x, mask_ratio=0.0)` (dreamvla_model.py:672-673).  The masking, the decoder's token un-shuffle and the loss are
+one kernel each (csrc/mae.hip); the blocks are the same fused blocks as everywhere else (decoder head_dim 32 runs on
+csrc/attention_hd.hip).
 
-Deviation (documented in DESIGN.md): the reference's `random_masking(x, 0.0)` (vit_mae.py:157-182,194) keeps
-all 196 patch tokens but in a random per-sample order and DreamVLA drops `ids_restore`.  Attention without
-positional terms after the embedding is permutation-equivariant, so the un-shuffled result is identical up
-to fp rounding (<= 6e-6 fp32).  This implementation keeps patch order (ids_restore =
-identity) and consumes no RNG.
+Deviations (documented in DESIGN.md):
+  * `random_masking(x, 0.0)` in the reference (vit_mae.py:157-182,194) keeps all patch tokens but in a random per-sample order,
+    and DreamVLA drops `ids_restore`.  Attention without positional terms after the embedding is permutation-equivariant, so
+    the un-shuffled result is identical up to fp rounding (<= 6e-6 fp32).  `forward_encoder(x, 0.0)`
+    keeps patch order (ids_restore = identity) and consumes no RNG.
+  * mask_ratio > 0: ids_shuffle is the STABLE ascending order of the noise (ties broken by index); the reference's
+    torch.argsort is not stable, so exact ties in the noise (about one sample in a thousand at L = 196) may order differently.
+  * `noise=` (random_masking, forward_encoder, forward) supplies the (N, L) fp32 noise instead of drawing torch.rand(N, L).
 """
 from functools import partial
 
@@ -61,14 +66,12 @@ class MaskedAutoencoderViT(nn.Module):
         self.blocks = nn.ModuleList([Block(embed_dim, num_heads, mlp_ratio, qkv_bias=True, norm_layer=norm_layer)
                                      for _ in range(depth)])
         self.norm = norm_layer(embed_dim)
-        # MAE decoder half: parameters only (never executed by DreamVLA)
+        # MAE decoder half (pretraining only: DreamVLA never runs it, but its tensors are part of the checkpoint)
         self.decoder_embed = Linear(embed_dim, decoder_embed_dim, bias=True)
         self.mask_token = nn.Parameter(torch.zeros(1, 1, decoder_embed_dim))
         self.decoder_pos_embed = nn.Parameter(torch.zeros(1, num_patches + 1, decoder_embed_dim), requires_grad=False)
-        self.decoder_blocks = nn.ModuleList([
-            Block(decoder_embed_dim, decoder_num_heads, mlp_ratio, qkv_bias=True, norm_layer=norm_layer)
-            if decoder_embed_dim // decoder_num_heads == 64 else _ParamOnlyBlock(decoder_embed_dim, mlp_ratio)
-            for _ in range(decoder_depth)])
+        self.decoder_blocks = nn.ModuleList([Block(decoder_embed_dim, decoder_num_heads, mlp_ratio, qkv_bias=True,
+                                                   norm_layer=norm_layer) for _ in range(decoder_depth)])
         self.decoder_norm = norm_layer(decoder_embed_dim)
         self.decoder_pred = Linear(decoder_embed_dim, patch_size ** 2 * in_chans, bias=True)
         self.norm_pix_loss = norm_pix_loss
@@ -95,11 +98,75 @@ class MaskedAutoencoderViT(nn.Module):
             nn.init.constant_(m.bias, 0)
             nn.init.constant_(m.weight, 1.0)
 
-    def forward_encoder(self, x, mask_ratio):
-        """x: (n, 3, H, W) -> (n, 1 + num_patches, embed_dim), mask (n, L) zeros, ids_restore identity."""
-        if mask_ratio != 0.0:
-            raise NotImplementedError("the DreamVLA hot path only calls forward_encoder(mask_ratio=0.0) "
-                                      "(models/dreamvla_model.py:672-673)")
+    def patchify(self, imgs):
+        """imgs (N, 3, H, W) -> (N, L, p*p*3)"""
+        p = self.patch_embed.patch_size[0]
+        assert imgs.shape[2] == imgs.shape[3] and imgs.shape[2] % p == 0
+        h = w = imgs.shape[2] // p
+        x = imgs.reshape(shape=(imgs.shape[0], 3, h, p, w, p))
+        x = torch.einsum('nchpwq->nhwpqc', x)
+        return x.reshape(shape=(imgs.shape[0], h * w, p ** 2 * 3))
+
+    def unpatchify(self, x):
+        """(N, L, p*p*3) -> imgs (N, 3, H, W)"""
+        p = self.patch_embed.patch_size[0]
+        h = w = int(x.shape[1] ** .5)
+        assert h * w == x.shape[1]
+        x = x.reshape(shape=(x.shape[0], h, w, p, p, 3))
+        x = torch.einsum('nhwpqc->nchpwq', x)
+        return x.reshape(shape=(x.shape[0], 3, h * p, h * p))
+
+    def random_masking(self, x, mask_ratio, noise=None):
+        """x (N, L, D) -> x_masked (N, len_keep, D), mask (N, L) (1 = removed), ids_restore (N, L); one kernel (ops.mae_random_masking)"""
+        N, L, D = x.shape
+        len_keep = int(L * (1 - mask_ratio))
+        if noise is None:
+            noise = torch.rand(N, L, device=x.device)
+        return ops.mae_random_masking(x, noise, len_keep)
+
+    def forward_encoder(self, x, mask_ratio, noise=None):
+        """x: (n, 3, H, W) -> latent (n, 1 + len_keep, embed_dim), mask (n, L), ids_restore (n, L).  mask_ratio 0.0 (DreamVLA's
+        frozen encoder): all patches in patch order, mask zeros, ids_restore identity, no RNG."""
+        if mask_ratio == 0.0:
+            return self._encode_all(x)
+        n = x.shape[0]
+        L = self.patch_embed.num_patches
+        x = self.patch_embed(x, pos=self.pos_embed[0, 1:, :])
+        len_keep = int(L * (1 - mask_ratio))
+        if noise is None:
+            noise = torch.rand(n, L, device=x.device)
+        # masking, the cls row and its position in one gather pass; the cls row's gradient is the column sum of row 0
+        x, mask, ids_restore = ops.mae_random_masking(x, noise, len_keep, cls_row=self.cls_token + self.pos_embed[:, :1, :])
+        for blk in self.blocks:
+            x = blk(x)
+        x = self.norm(x)
+        return x, mask, ids_restore
+
+    def _decode(self, x, ids_restore):
+        """forward_decoder with the cls row kept: (N, 1 + L, p*p*3)"""
+        x = self.decoder_embed(x)
+        x = ops.mae_unshuffle(x, self.mask_token, ids_restore, self.decoder_pos_embed)
+        for blk in self.decoder_blocks:
+            x = blk(x)
+        x = self.decoder_norm(x)
+        return self.decoder_pred(x)
+
+    def forward_decoder(self, x, ids_restore):
+        """latent (N, 1 + len_keep, embed_dim) -> pred (N, L, p*p*3)"""
+        return self._decode(x, ids_restore)[:, 1:, :]
+
+    def forward_loss(self, imgs, pred, mask):
+        """imgs (N, 3, H, W), pred (N, L, p*p*3), mask (N, L) -> mean loss on the removed patches (patchify fused in)"""
+        return ops.mae_loss(pred, imgs, mask, self.patch_embed.patch_size[0], self.norm_pix_loss)
+
+    def forward(self, imgs, mask_ratio=0.75, noise=None):
+        latent, mask, ids_restore = self.forward_encoder(imgs, mask_ratio, noise=noise)
+        full = self._decode(latent, ids_restore)
+        # the loss reads rows 1..L of the decoder output in place; its gradient comes back with the cls rows zero
+        loss = ops.mae_loss(full, imgs, mask, self.patch_embed.patch_size[0], self.norm_pix_loss)
+        return loss, full[:, 1:, :], mask
+
+    def _encode_all(self, x):
         n = x.shape[0]
         L = self.patch_embed.num_patches
         # patch-embed GEMM + bias; the fixed pos-embed add rides in the residual slot of the epilogue
@@ -116,22 +183,3 @@ class MaskedAutoencoderViT(nn.Module):
         mask = torch.zeros(n, L, device=x.device)
         ids_restore = torch.arange(L, device=x.device).unsqueeze(0).expand(n, -1)
         return x, mask, ids_restore
-
-
-class _ParamOnlyBlock(nn.Module):
-    """Holds timm-Block-shaped parameters for head_dim != 64 blocks that are never executed (MAE decoder:
-    512 wide / 16 heads = 32)."""
-
-    def __init__(self, dim, mlp_ratio):
-        super().__init__()
-        self.norm1 = LayerNorm(dim)
-        self.attn = nn.Module()
-        self.attn.qkv = Linear(dim, dim * 3, bias=True)
-        self.attn.proj = Linear(dim, dim)
-        self.norm2 = LayerNorm(dim)
-        self.mlp = nn.Module()
-        self.mlp.fc1 = Linear(dim, int(dim * mlp_ratio))
-        self.mlp.fc2 = Linear(int(dim * mlp_ratio), dim)
-
-    def forward(self, x):
-        raise NotImplementedError("MAE decoder blocks are not on the DreamVLA hot path")

@@ -392,6 +392,50 @@ int dvla_mask_tables(const dvla_mask_rule* rule, const int32_t* drop, int32_t* k
 int dvla_image_preprocess(const uint8_t* src, const int32_t* shift, void* out, int64_t n, int32_t height, int32_t width,
                           int32_t pad, const float* mean3, const float* std3, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * MAE pretraining (models/vit_mae.py:129-256): random masking, the decoder's token un-shuffle and the patch-MSE loss, each
+ * one pass instead of the reference's argsort / gather / cat / add / patchify / mean / var chains.  Deterministic: no float
+ * atomics, fixed-order two-stage sums.  bf16 activations, fp32 arithmetic; all tensors contiguous unless a stride is given,
+ * every bf16 row base 16-byte aligned.
+ *
+ * dvla_mae_mask_fwd: per sample n, ids_shuffle = the ascending order of noise[n, :] with ties broken by index (exactly
+ * torch.argsort(noise, dim=1, stable=True)); ids_restore[n, ids_shuffle[r]] = r (int64); mask[n, l] = (ids_restore[n, l] >=
+ * len_keep) in {0, 1} fp32; out (N, c + len_keep, D) = [cls_row ; x[n, ids_shuffle[n, :len_keep]]] where c = 1, or c = 0 and no
+ * cls row when cls_row is NULL.  noise (N, L) fp32, x (N, L, D) bf16, cls_row (D,) bf16.  L <= 1024, 0 < len_keep <= L,
+ * D % 8 == 0, else DVLA_ERR_UNSUPPORTED.
+ * dvla_mae_mask_bwd: dx (N, L, D) = dout's row c + ids_restore[n, l] where that is a kept row, else 0 (the cls row's gradient
+ * is the caller's column sum of dout[:, 0, :]).  ids_restore outside [0, L) reads as removed. */
+int dvla_mae_mask_fwd(const float* noise, const void* x, const void* cls_row, int32_t N, int32_t L, int32_t D, int32_t len_keep,
+                      int64_t* ids_restore, float* mask, void* out, void* stream);
+int dvla_mae_mask_bwd(const int64_t* ids_restore, const void* dout, int32_t has_cls, int32_t N, int32_t L, int32_t D,
+                      int32_t len_keep, void* dx, void* stream);
+/* dvla_mae_unshuffle_fwd (models/vit_mae.py:213-219): out (N, 1 + L, D) with out[n, 0] = y[n, 0] + pos[0] and out[n, 1 + l] =
+ * (r = ids_restore[n, l] in [0, len_keep) ? y[n, 1 + r] : mask_token) + pos[1 + l], each element one fp32 add of the bf16
+ * operands rounded once (ATen's bf16 add).  y (N, 1 + len_keep, D), mask_token (D,), pos (1 + L, D), all bf16.
+ * dvla_mae_unshuffle_bwd: dy (N, 1 + len_keep, D) bf16 = the gather of dout's cls row and kept rows (rows of dy that no
+ * ids_restore entry names are zero); dmask_token (D,) in dmask_dtype = the fp32 sum over all removed rows of all samples in a
+ * fixed order, rounded once.  `partial` = 4 * N * D floats of workspace.  D % 8 == 0 and D <= 2048, L <= 1024, N <= 65535 (also
+ * for dvla_mae_mask_bwd). */
+int dvla_mae_unshuffle_fwd(const void* y, const void* mask_token, const int64_t* ids_restore, const void* pos, int32_t N, int32_t L,
+                           int32_t D, int32_t len_keep, void* out, void* stream);
+int dvla_mae_unshuffle_bwd(const void* dout, const int64_t* ids_restore, int32_t N, int32_t L, int32_t D, int32_t len_keep, void* dy,
+                           void* dmask_token, int32_t dmask_dtype, float* partial, void* stream);
+/* dvla_mae_loss_fwd / _bwd (models/vit_mae.py:129-141,234-250): forward_loss fused with patchify.  Sample n's L = (H / p) (W / p)
+ * patch predictions are the bf16 rows pred + n * pred_stride_n + (row0 + l) * pred_stride_r, P = 3 p^2 contiguous elements
+ * each; element e = (py p + px) 3 + c of patch l = ph (W / p) + pw is imgs[n, c, ph p + py, pw p + px] ('nchpwq->nhwpqc').
+ * norm_pix != 0: the target is (t - mean) / sqrt(var + 1e-6) per patch, var unbiased.  mask (N, L) fp32.
+ * fwd: out2[0] = sum(mask * mean_P((pred - target)^2)) / sum(mask), out2[1] = sum(mask); partial = dvla_mae_loss_partial_len()
+ * floats.  bwd: dpred (N, row0 + L, P) bf16 contiguous = grad_out[0] * dloss/dpred (out2[1] from the forward), rows < row0
+ * zero.  p <= 16, imgs_dtype fp32 or bf16, H and W multiples of p, else DVLA_ERR_UNSUPPORTED. */
+typedef struct dvla_mae_loss_params {
+  const void* pred; int64_t pred_stride_n; int64_t pred_stride_r; int32_t row0; int32_t patch;
+  const void* imgs; int32_t imgs_dtype; int32_t norm_pix; int32_t H; int32_t W;
+  const float* mask; int64_t N;
+} dvla_mae_loss_params;
+int64_t dvla_mae_loss_partial_len(void);
+int dvla_mae_loss_fwd(const dvla_mae_loss_params* p, float* out2, float* partial, void* stream);
+int dvla_mae_loss_bwd(const dvla_mae_loss_params* p, const float* out2, const float* grad_out, void* dpred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
