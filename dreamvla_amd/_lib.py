@@ -145,6 +145,7 @@ SYMBOLS = {
     "dvla_silog_loss_bwd": (C.c_int, [C.POINTER(FrameView), C.POINTER(FrameView), _I64, _F, _P, _P, C.POINTER(FrameView), _P]),
     "dvla_sumsq_partial_len": (C.c_int64, []),
     "dvla_sumsq_bf16": (C.c_int, [_P, _I64, _P, _P, C.c_int32, _P]),
+    "dvla_sumsq_f32": (C.c_int, [_P, _I64, _P, _P, C.c_int32, _P]),
     "dvla_mae_mask_fwd": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "dvla_mae_mask_bwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "dvla_mae_unshuffle_fwd": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P]),
@@ -154,6 +155,8 @@ SYMBOLS = {
     "dvla_mae_loss_bwd": (C.c_int, [C.POINTER(MaeLossParams), _P, _P, _P, _P]),
     "dvla_adamw_bf16": (C.c_int, [_P, _P, _P, _P, _I64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I64, _P,
                                   C.c_float, _P]),
+    "dvla_adamw_f32_master": (C.c_int, [_P, _P, _P, _P, _P, _I64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                        _I64, _P, C.c_float, _P]),
 }
 
 _lib = None

@@ -9,6 +9,13 @@
 //                     one read-modify-write pass: 2 B (g) + 3 x (2 + 2) B (p, m, v) = 14 B / parameter.
 // Element-wise semantics follow torch's fused AdamW with bf16 parameters (state in the parameter dtype) and
 // clip_grad_norm_ (the gradient is rounded to bf16 after scaling, as the in-place `grad.mul_(coef)` does).
+//
+// fp32 masters (the shipped `--precision fp32` runs: parameters, gradients and both moments fp32):
+//   dvla_sumsq_f32        : the fp32 twin of dvla_sumsq_bf16, same two-stage reduction, same device scalar (one clip norm
+//                           can span bf16 and fp32 buckets)
+//   dvla_adamw_f32_master : clip (in fp32) + AdamW restating torch's foreach AdamW on fp32 parameters operation for
+//                           operation, and the bf16 compute shadow of the new master written in the same pass:
+//                           4 B (g) + 3 x (4 + 4) B (p, m, v) + 2 B (shadow) = 30 B / parameter.
 #include "common.h"
 #include "../../include/dvla.h"
 
@@ -99,6 +106,87 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a) {
     }
 }
 
+__global__ __launch_bounds__(256) void sumsq_f32_partial_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ partial) {
+  __shared__ float red[4];
+  const int64_t nvec = n >> 2;
+  float s = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
+    const float4 u = reinterpret_cast<const float4*>(x)[i];
+    s = fmaf(u.x, u.x, s); s = fmaf(u.y, u.y, s); s = fmaf(u.z, u.z, s); s = fmaf(u.w, u.w, s);
+  }
+  if (blockIdx.x == 0)   // ragged tail (n % 4 elements)
+    for (int64_t i = (nvec << 2) + threadIdx.x; i < n; i += 256) { const float a = x[i]; s = fmaf(a, a, s); }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
+// Scalars derived on the host exactly as torch/optim/adam.py derives them from the Python (double) hyper-parameters, then
+// handed to the element-wise ops as fp32 (the foreach kernels' opmath scalars).
+struct MasterArgs {
+  float* p; const float* g; float* m; float* v; bf16_t* sh; int64_t n;
+  float decay;        // 1 - lr * wd                      (_foreach_mul_(params, 1 - lr * weight_decay))
+  float w1;           // 1 - beta1                        (_foreach_lerp_(exp_avgs, grads, 1 - beta1))
+  int w1_small;       // |w1| < 0.5: ATen lerp's branch
+  float beta2, omb2;  // beta2, 1 - beta2                 (_foreach_mul_(exp_avg_sqs, beta2); _foreach_addcmul_(.., g, g, 1 - beta2))
+  float bc2_sqrt;     // sqrt(1 - beta2^step)             (_foreach_div_(sqrt(v), bc2_sqrt))
+  float eps;          //                                  (_foreach_add_(.., eps))
+  float step_size;    // -lr / (1 - beta1^step)           (_foreach_addcdiv_(params, m, denom, step_size))
+  const float* sumsq; float max_norm;
+};
+
+// One element.  Every torch foreach op is a separate kernel, so its result is rounded to fp32 before the next op sees it
+// (explicit _rn intrinsics: the compiler must not contract across them); WITHIN one ATen element function the expression is
+// compiled as written (a + b * c contracts to one fma: lerp, addcmul, addcdiv).
+__device__ __forceinline__ void master_one(float& p, float g, float& m, float& v, const MasterArgs& a, float coef) {
+  if (a.sumsq) g = __fmul_rn(g, coef);                          // clip_grad_norm_: _foreach_mul_(grads, clip_coef), fp32
+  p = __fmul_rn(p, a.decay);                                    // decoupled weight decay
+  const float d = __fsub_rn(g, m);                              // exp_avg.lerp_(grad, w1)
+  m = a.w1_small ? fmaf(a.w1, d, m) : fmaf(-d, 1.0f - a.w1, g);
+  v = __fmul_rn(v, a.beta2);                                    // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2)
+  v = fmaf(a.omb2, __fmul_rn(g, g), v);
+  const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), a.bc2_sqrt), a.eps);   // (sqrt(v) / bc2_sqrt) + eps
+  p = fmaf(a.step_size, __fdiv_rn(m, denom), p);                // p.addcdiv_(m, denom, -lr / bc1)
+}
+
+__global__ __launch_bounds__(256) void adamw_master_kernel(MasterArgs a) {
+  float coef = 1.0f;
+  if (a.sumsq) {
+    const float c = a.max_norm / (sqrtf(a.sumsq[0]) + 1e-6f);
+    coef = c < 1.0f ? c : 1.0f;
+  }
+  const int64_t nvec = a.n >> 3;      // 8 elements per thread: 2 x 16 B of each fp32 stream, 16 B of shadow
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
+    float4 p4[2], g4[2], m4[2], v4[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      p4[h] = reinterpret_cast<const float4*>(a.p)[2 * i + h]; g4[h] = reinterpret_cast<const float4*>(a.g)[2 * i + h];
+      m4[h] = reinterpret_cast<const float4*>(a.m)[2 * i + h]; v4[h] = reinterpret_cast<const float4*>(a.v)[2 * i + h];
+    }
+    uint32_t sh[4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      master_one(p4[h].x, g4[h].x, m4[h].x, v4[h].x, a, coef);
+      master_one(p4[h].y, g4[h].y, m4[h].y, v4[h].y, a, coef);
+      master_one(p4[h].z, g4[h].z, m4[h].z, v4[h].z, a, coef);
+      master_one(p4[h].w, g4[h].w, m4[h].w, v4[h].w, a, coef);
+      sh[2 * h] = pack2bf(p4[h].x, p4[h].y); sh[2 * h + 1] = pack2bf(p4[h].z, p4[h].w);
+      reinterpret_cast<float4*>(a.p)[2 * i + h] = p4[h];
+      reinterpret_cast<float4*>(a.m)[2 * i + h] = m4[h];
+      reinterpret_cast<float4*>(a.v)[2 * i + h] = v4[h];
+    }
+    if (a.sh) reinterpret_cast<uint4*>(a.sh)[i] = make_uint4(sh[0], sh[1], sh[2], sh[3]);
+  }
+  if (blockIdx.x == 0)
+    for (int64_t i = (nvec << 3) + threadIdx.x; i < a.n; i += 256) {
+      float p = a.p[i], m = a.m[i], v = a.v[i];
+      master_one(p, a.g[i], m, v, a, coef);
+      a.p[i] = p; a.m[i] = m; a.v[i] = v;
+      if (a.sh) a.sh[i] = f2bf(p);
+    }
+}
+
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
@@ -137,5 +225,47 @@ extern "C" int dvla_adamw_bf16(void* param, const void* grad, void* exp_avg, voi
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+  return dvla_check_launch();
+}
+
+extern "C" int dvla_sumsq_f32(const float* x, int64_t n, float* partial, float* out, int32_t accumulate, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (!x || !partial || !out || n < 0) return DVLA_ERR_ARG;
+  if (!al16(x)) return DVLA_ERR_UNSUPPORTED;
+  int64_t blocks = (n / 4 + 255) / 256;
+  if (blocks > SS_BLOCKS) blocks = SS_BLOCKS;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(sumsq_f32_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, n, partial);
+  int rc = dvla_check_launch();
+  if (rc != DVLA_OK) return rc;
+  hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, stream, partial, (int)blocks, out, (int)accumulate);
+  return dvla_check_launch();
+}
+
+extern "C" int dvla_adamw_f32_master(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
+                                     int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay,
+                                     int64_t step, const float* grad_sumsq, float max_norm, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (!param || !grad || !exp_avg || !exp_avg_sq || n < 0 || step < 1) return DVLA_ERR_ARG;
+  if (n == 0) return DVLA_OK;
+  if (!al16(param) || !al16(grad) || !al16(exp_avg) || !al16(exp_avg_sq) || (shadow_bf16 && !al16(shadow_bf16)))
+    return DVLA_ERR_UNSUPPORTED;
+  MasterArgs a;
+  a.p = param; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.sh = reinterpret_cast<bf16_t*>(shadow_bf16); a.n = n;
+  // the scalars as torch/optim/adam.py (_multi_tensor_adam, capturable=False) computes them in Python floats
+  a.decay = (float)(1.0 - lr * weight_decay);
+  a.w1 = (float)(1.0 - beta1);
+  a.w1_small = fabsf(a.w1) < 0.5f;
+  a.beta2 = (float)beta2;
+  a.omb2 = (float)(1.0 - beta2);
+  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+  a.bc2_sqrt = (float)pow(bc2, 0.5);
+  a.eps = (float)eps;
+  a.step_size = (float)((lr / bc1) * -1.0);
+  a.sumsq = grad_sumsq; a.max_norm = max_norm;
+  int64_t blocks = (n / 8 + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(adamw_master_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
   return dvla_check_launch();
 }

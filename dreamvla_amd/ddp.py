@@ -233,6 +233,7 @@ class GradBucketReducer:
         for b in self.buckets[self._next_launch:]:
             self._launch(b)
         for b in self.buckets:
+            b["ever_fired"] = b.get("ever_fired", False) or any(b["fired"])     # (FlatAdamW master mode skips never-fired buckets)
             if self.static_unused and any(b["fired"]):
                 if b["hold"]:                       # grew: wait for everything seen so far
                     b["expected"] = [e or f for e, f in zip(b["expected"], b["fired"])]

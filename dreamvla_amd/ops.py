@@ -913,29 +913,82 @@ class _Shadow(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, w):
-        import weakref
+        ctx.master = w
         ent = _Shadow.cache.get(id(w))
         if (ent is not None and ent[0]() is w and ent[1] == w._version and ent[2] == w.data_ptr() and ent[3] == w.device):
             return ent[4]
         sh = cast_to(w.detach(), BF16)
-        if len(_Shadow.cache) > 4096:
-            _Shadow.cache.clear()
-        _Shadow.cache[id(w)] = (weakref.ref(w), w._version, w.data_ptr(), w.device, sh, bool(w.requires_grad))
+        _Shadow.remember(w, sh)
         return sh
 
     @staticmethod
+    def remember(w, sh):
+        import weakref
+        if len(_Shadow.cache) > 4096:
+            _Shadow.cache.clear()
+        _Shadow.cache[id(w)] = (weakref.ref(w), w._version, w.data_ptr(), w.device, sh, bool(w.requires_grad))
+
+    @staticmethod
     def backward(ctx, g):
-        return cast_to(g.contiguous(), torch.float32) if g.dtype == BF16 else g.float()
+        if g.dtype != BF16:
+            return g.float()
+        g = g.contiguous()
+        dst = _grad_dest(ctx.master, torch.float32)     # the master's fp32 bucket slot: widen straight into it
+        if dst is None:
+            return cast_to(g, torch.float32)
+        check(_lib.load().dvla_cast_bf16_to_f32(g.data_ptr(), dst.data_ptr(), g.numel(), _stream()), "dvla_cast")
+        return dst
+
+
+# (flat master buffer, flat bf16 shadow buffer) pairs whose shadows an optimizer keeps current (dreamvla_amd.optim.FlatAdamW
+# in master mode writes the bf16 copy of every master it steps, in the same kernel)
+_FLAT_SHADOWS = []
+
+
+def register_flat_shadow(flat_master, flat_shadow):
+    """declare that `flat_shadow` (bf16) holds, at the same element offsets, the shadows of masters living in `flat_master`
+    (fp32), rewritten by whoever steps those masters (see adopt_shadow)"""
+    import weakref
+    _FLAT_SHADOWS[:] = [(m, s) for m, s in _FLAT_SHADOWS if m() is not None and s() is not None]
+    _FLAT_SHADOWS.append((weakref.ref(flat_master), weakref.ref(flat_shadow)))
+
+
+def adopt_shadow(w, sh):
+    """make `sh` (a view of a registered flat shadow buffer, already holding RNE-bf16 of the master's current value) the cached
+    shadow of master `w`, recorded at its current version and address: the next forward issues no cast for it"""
+    _Shadow.remember(w, sh)
+
+
+def _optimizer_maintained(e):
+    """cache entry whose shadow an optimizer rewrote at the current value of its master: the shadow lies in a registered flat
+    shadow buffer, the master still lives at the same offset of the matching flat master buffer, and neither its version
+    nor its address moved since the entry was recorded"""
+    w = e[0]()
+    if w is None or e[1] != w._version or e[2] != w.data_ptr():
+        return False
+    sh = e[4]
+    for m_ref, s_ref in _FLAT_SHADOWS:
+        m, s = m_ref(), s_ref()
+        if m is None or s is None:
+            continue
+        s0 = s.data_ptr()
+        if not (s0 <= sh.data_ptr() < s0 + 2 * s.numel()):
+            continue
+        off = (sh.data_ptr() - s0) // 2
+        return w.data_ptr() == m.data_ptr() + 4 * off and off + w.numel() <= m.numel()
+    return False
 
 
 def invalidate_shadows(trainable_only=False):
     """Forget the cached bf16 shadows of fp32 master weights (all of them, or only those of weights with requires_grad):
     the next forward re-casts from the masters.  Called automatically after every torch `Optimizer.step()`; call it yourself
-    after updating masters through `.data` / raw pointers outside an optimizer."""
+    after updating masters through `.data` / raw pointers outside an optimizer.  trainable_only=True (the post-step hook)
+    keeps the entries an optimizer has just rewritten in a registered flat shadow buffer (FlatAdamW master mode); a call
+    without arguments drops those too."""
     if not trainable_only:
         _Shadow.cache.clear()
         return
-    for k in [k for k, e in _Shadow.cache.items() if e[5] or e[0]() is None]:
+    for k in [k for k, e in _Shadow.cache.items() if e[0]() is None or (e[5] and not _optimizer_maintained(e))]:
         del _Shadow.cache[k]
 
 

@@ -323,6 +323,19 @@ int dvla_sumsq_bf16(const void* x, int64_t n, float* partial, float* out, int32_
 int dvla_adamw_bf16(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, float lr, float beta1,
                     float beta2, float eps, float weight_decay, int64_t step, const float* grad_sumsq, float max_norm,
                     void* stream);
+/* fp32 masters (`--precision fp32`: parameters, gradients and both moments fp32).
+ * dvla_sumsq_f32: the fp32 twin of dvla_sumsq_bf16 (same reduction, same `partial` / `out` contract): calls on bf16 and
+ *   fp32 buffers can accumulate into one device scalar.
+ * dvla_adamw_f32_master: one clip + AdamW step on n fp32 elements, restating torch's foreach AdamW for fp32 parameters
+ *   operation for operation (decoupled weight decay; each torch op rounded to fp32): the clip coefficient
+ *   min(1, max_norm / (sqrt(*grad_sumsq) + 1e-6)) scales the gradient in fp32 (grad_sumsq NULL: no clipping).  The
+ *   hyper-parameters are doubles (the Python floats torch derives its scalars from).  If shadow_bf16 != NULL it receives
+ *   the round-to-nearest-even bf16 copy of the new parameter (bit-identical to dvla_cast_f32_to_bf16 of it).  Every
+ *   pointer is 16-byte aligned; `step` is the 1-based step count. */
+int dvla_sumsq_f32(const float* x, int64_t n, float* partial, float* out, int32_t accumulate, void* stream);
+int dvla_adamw_f32_master(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, int64_t n,
+                          double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                          const float* grad_sumsq, float max_norm, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Token assembly (models/dreamvla_model.py:739-759): out[b, s, t, :] = part_k[b, s, t - tok_begin_k, :] + pos[s, :]
