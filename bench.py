@@ -11,16 +11,24 @@ heads, DiT diffusion head) -> reference loss block -> backward -> gradient all-r
 (B = 32 per GPU, S = 7, 2 x 224^2 views, 77 text tokens) with the head set of the shipped CALVIN finetune script
 (obs + depth + sam dream heads, DiT head; L = 651).  rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+A plain run does only what the headline needs: set up (model, batch, GEMM tuner steps or a plan), warm up, time the steps,
+write --dump-outputs if asked, print the line.  The legs below run after the timed region, and only with --full (each can
+then be left out with its --no-* option); without --full their objects in the line are null.
+
+Extra objects in the line (--full):
+  fwd_ms_per_step : forward-only latency (train mode, autograd graph recorded, no backward), 3 steps after 1 un-timed.
   roofline     : the dominant kernels (gemm_ring_kernel / gemm_kernel, bf16 MFMA).  achieved = algorithmic FLOPs of every GEMM launch of one
                  instrumented step / summed launch durations (HIP events on the launch stream), peak = 2500 TFLOP/s dense.
   cpu_baseline : the oracle (oracle/model_ref.py, "port") timed on this box's host cores on a bounded sample (B = 2).
   eager_rocm_baseline : the same step run eagerly on PyTorch-ROCm bf16 on this GPU (the >= 4x target's denominator).
+  loss_parity  : the loss of the trained HIP module against the oracle restatement in fp32 / bf16 on this GPU (loss_parity()).
+  integration_levels : the untouched reference loop / + HIP loss block / headline configuration (integration_levels()).
+  rollout      : BASELINE configs[4], 64 episodes in lock-step through the hipGraph-captured engine (tests/gpu_rollout_bench.py).
   other_configs : after the timed region, a few steps each of the configurations BASELINE.json names next to the headline one --
                  head set E (all dream heads, configs[3]), head set D driven with the LIBERO flags of finetune_long.sh (B = 16,
                  4-pass gradient accumulation through reducer.no_sync()), head set C at CALVIN's own window S = 10 (finetune.sh:37).
-  rccl (N > 1) : what the collective layer saw -- ranks counted by an all-reduce over the RCCL group, buckets, bytes, how many
-                 buckets launched during backward, whether the robust GEMM schedule engaged.
+  rccl (N > 1 or --torch-ddp) : what the collective layer saw -- ranks counted by an all-reduce over the RCCL group, buckets,
+                 bytes, how many buckets launched during backward, whether the robust GEMM schedule engaged.
 --torch-ddp / --torch-adamw select the UNCHANGED caller's path (train.py:173-174, utils/train_utils.py:598-608: torch DDP with
 find_unused_parameters, clip_grad_norm_, torch.optim.AdamW) at any N, N = 1 included (a one-rank RCCL group).
 --dump-outputs DIR writes what the last timed step computed as .npy files (dump_outputs), so that two builds can be compared output
@@ -480,7 +488,27 @@ def require_finite_loss(loss_val):
     return loss_val
 
 
-def main():
+def extra_legs(args, rank, world):
+    """The legs this rank runs after the timed region: none without --full; with it, every leg whose --no-* option is not given
+    and that applies to this rank, world size, head set and path."""
+    if not args.full:
+        return frozenset()
+    alone = rank == 0 and world == 1
+    on = {
+        "fwd": (rank == 0 or world > 1) and not args.no_fwd,
+        "roofline": not args.no_roofline,
+        "loss_parity": alone and not args.no_loss_parity,
+        "cpu_baseline": alone and not args.no_cpu_baseline,
+        "eager_baseline": alone and not args.no_eager_baseline,
+        "integration_levels": alone and not args.no_integration_levels and not args.torch_ddp,
+        "rollout": alone and not args.no_rollout and args.heads == "C",
+        "other_configs": alone and not args.no_other_configs and args.heads == "C" and not args.torch_ddp,
+        "rccl": world > 1 or args.torch_ddp,
+    }
+    return frozenset(k for k, v in on.items() if v)
+
+
+def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=8)
@@ -503,6 +531,10 @@ def main():
     ap.add_argument("--torch-profile", default=None, metavar="FILE",
                     help="diagnostics: after the timed region, one more step under torch.profiler; ATen / autograd operators by "
                          "device time (with input shapes) are written to FILE")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the legs below (forward-only latency, roofline, loss parity, CPU and eager "
+                         "baselines, integration levels, rollout, other configurations; the rccl block at N > 1 or with --torch-ddp): "
+                         "~90 s more at N = 1.  Without it those objects of the line are null")
     ap.add_argument("--no-fwd", action="store_true", help="skip the forward-only latency leg (counter passes: whole steps only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
@@ -529,6 +561,11 @@ def main():
     ap.add_argument("--torch-ddp", action="store_true", help="use torch DDP instead of dreamvla_amd.ddp.GradBucketReducer")
     ap.add_argument("--torch-adamw", action="store_true",
                     help="clip_grad_norm_ + torch.optim.AdamW(fused) instead of dreamvla_amd.optim.FlatAdamW (HIP, flat buffers)")
+    return ap
+
+
+def main():
+    ap = make_parser()
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -649,8 +686,9 @@ def main():
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    legs = extra_legs(args, rank, world)
     rccl = None
-    if world > 1 or args.torch_ddp:
+    if "rccl" in legs:
         ones = torch.ones(1, device=dev)
         dist.all_reduce(ones)                                      # over the RCCL group: how many ranks the collective layer sees
         rccl = {"backend": dist.get_backend(), "ranks_seen_by_all_reduce": int(ones.item()), "world_size": world}
@@ -681,7 +719,7 @@ def main():
 
     # forward-only latency (train mode, autograd graph recorded, no backward)
     fwd_ms = None
-    if (rank == 0 or world > 1) and not args.no_fwd:
+    if "fwd" in legs:
         for _ in range(1):
             forward_loss()
         torch.cuda.synchronize()
@@ -692,7 +730,7 @@ def main():
         fwd_ms = (time.perf_counter() - t1) / 3 * 1e3
 
     roofline = None
-    if not args.no_roofline:
+    if "roofline" in legs:
         prof = ops.GemmProfiler()
         with prof:
             step()
@@ -725,14 +763,14 @@ def main():
                     "tuner_wins_by_problem_key": GemmTuner.summary()}
 
     parity = None
-    if rank == 0 and world == 1 and not args.no_loss_parity:
+    if "loss_parity" in legs:
         try:
             parity = loss_parity(model, cfg, batch, lab, inputs, S, B, dev)
         except Exception as e:  # noqa: BLE001
             parity = {"rel": None, "sample": f"failed: {e!r}"}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if "cpu_baseline" in legs:
         try:
             cpu = cpu_baseline(args.heads, S)
         except Exception as e:  # noqa: BLE001
@@ -743,7 +781,7 @@ def main():
     optimizer_name = ("FlatAdamW (HIP: dvla_sumsq_bf16 + dvla_adamw_bf16 on flat buffers)" if flat_opt is not None
                       else "clip_grad_norm_ + torch.optim.AdamW (train.py:174 as written: no fused=)" if args.torch_ddp
                       else "clip_grad_norm_ + torch.optim.AdamW(fused=True)")
-    if rank == 0 and world == 1 and not args.no_eager_baseline:
+    if "eager_baseline" in legs:
         try:
             model = ddp_model = reducer = flat_opt = opt = params = None
             torch.cuda.empty_cache()
@@ -753,7 +791,7 @@ def main():
             eager = {"value": None, "unit": "samples/s", "sample": f"failed: {e!r}"}
 
     levels = None
-    if rank == 0 and world == 1 and not args.no_integration_levels and not args.torch_ddp:
+    if "integration_levels" in legs:
         try:
             model = ddp_model = reducer = flat_opt = opt = params = None      # (the timed objects: loss_parity above was their last user)
             torch.cuda.empty_cache()
@@ -763,7 +801,7 @@ def main():
         torch.cuda.empty_cache()
 
     rollout = None
-    if rank == 0 and world == 1 and not args.no_rollout and args.heads == "C":
+    if "rollout" in legs:
         try:
             from tests import gpu_rollout_bench
             torch.cuda.empty_cache()
@@ -780,7 +818,7 @@ def main():
             rollout = {"value": None, "sample": f"failed: {e!r}"}
 
     others = None
-    if rank == 0 and world == 1 and not args.no_other_configs and args.heads == "C" and not args.torch_ddp:
+    if "other_configs" in legs:
         others = {}
         for (name, heads_o, S_o, B_o, accum, extra_cfg, loss_kw, batch_kw) in OTHER_CONFIGS:
             try:
@@ -795,6 +833,7 @@ def main():
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
             "fwd_ms_per_step": fwd_ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "bf16", "data": "synthetic", "gemm_plan": os.path.relpath(plan, ROOT) if plan and os.path.exists(plan) else None,
+            "full": args.full,
             "config": {"workload": f"DreamVLA CALVIN {args.phase} step, head set {args.heads} "
                                    f"({'+'.join(k for k in HEAD_SETS[args.heads] if HEAD_SETS[args.heads][k])}), "
                                    f"B={B}/GPU, S={S}, window {S + 3}, 2x224^2 views, 77 text tokens, hidden 1024 / "

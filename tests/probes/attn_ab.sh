@@ -14,7 +14,7 @@ timeout 90 python tests/gpu_attn_perf.py > $OUT/r05y_attn_perf_new.jsonl 2> $OUT
 echo "perf new rc=$?" >> $OUT/r05y_rc.txt
 DVLA_LIB=$PWD/build/ab/libdvla_before_attn.so timeout 90 python tests/gpu_attn_perf.py > $OUT/r05y_attn_perf_old.jsonl 2> $OUT/r05y_perf_old.err
 echo "perf old rc=$?" >> $OUT/r05y_rc.txt
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-eager-baseline --no-rollout --no-loss-parity --no-other-configs --plan profiles/r05_gemm_plan.json"
+B="python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-eager-baseline --no-rollout --no-loss-parity --no-other-configs --plan profiles/r05_gemm_plan.json"
 timeout 120 $B > $OUT/r05y_bench_new.json 2> $OUT/r05y_bench_new.err
 echo "bench new rc=$?" >> $OUT/r05y_rc.txt
 DVLA_LIB=$PWD/build/ab/libdvla_before_attn.so timeout 120 $B > $OUT/r05y_bench_old.json 2> $OUT/r05y_bench_old.err

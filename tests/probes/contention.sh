@@ -18,7 +18,7 @@ for l in sys.stdin:
     print('  %dx%dx%-5d ' % (r['M'], r['N'], r['K']) + '  '.join('%s %7.1f' % (k, v['us']) for k, v in r.items() if k.startswith('v') and isinstance(v, dict)))" >> $O
   done
 done
-B="python bench.py --no-cpu-baseline --no-eager-baseline --no-rollout --no-loss-parity --no-other-configs --no-integration-levels --no-fwd --steps 10 --warmup 2"
+B="python bench.py --full --no-cpu-baseline --no-eager-baseline --no-rollout --no-loss-parity --no-other-configs --no-integration-levels --no-fwd --steps 10 --warmup 2"
 for tag in default robust; do
   if [ $tag = robust ]; then export DVLA_GEMM_OVERSUBSCRIBE=8 DVLA_GEMM_STREAMK=0; fi
   timeout 600 $B 2> /dev/null | tail -1 | python -c "

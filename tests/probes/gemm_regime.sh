@@ -3,7 +3,7 @@
 # with the library from before them -- same GEMM code objects, same plan, same box.  Per-shape breakdowns of both, side by side.
 set -u
 OUT=gpurun_out; mkdir -p $OUT
-B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-eager-baseline --no-rollout --no-loss-parity --no-other-configs --no-integration-levels"
+B="python bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-eager-baseline --no-rollout --no-loss-parity --no-other-configs --no-integration-levels"
 timeout 200 $B --save-plan $OUT/r06g_plan.json > $OUT/r06g_bench_tune.json 2> $OUT/r06g.err
 for i in 1 2; do
 DVLA_GEMM_BREAKDOWN=$OUT/r06g_bd_old$i.json DVLA_LIB=$PWD/build/ab/libdvla_before_r6attn.so timeout 120 $B --plan $OUT/r06g_plan.json > $OUT/r06g_bench_old$i.json 2>> $OUT/r06g.err

@@ -1,6 +1,6 @@
 set -u
 OUT=gpurun_out; mkdir -p $OUT
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-eager-baseline --no-rollout --no-loss-parity --no-other-configs --no-integration-levels"
+B="python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-eager-baseline --no-rollout --no-loss-parity --no-other-configs --no-integration-levels"
 rocm-smi --showclocks 2>/dev/null | head -20 > $OUT/r06m_clocks.txt
 timeout 200 $B --save-plan $OUT/r06m_plan.json > $OUT/r06m_bench_new.json 2> $OUT/r06m_bench_new.err
 for i in 1 2; do
