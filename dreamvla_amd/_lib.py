@@ -126,8 +126,10 @@ SYMBOLS = {
     "dvla_act_bwd_colsum": (C.c_int, [_P, _P, _P, _I64, _I64, _I32, _F, _U32, _U32, _P, _I32, _P, _P]),
     "dvla_act_fwd": (C.c_int, [_P, _P, _I64, _I32, _P]),
     "dvla_ddim_cfg_step": (C.c_int, [_P, _I64, _P, _P, _I64, _I64, _F, _F, _F, _F, _F, _P]),
+    "dvla_fm_cfg_step": (C.c_int, [_P, _I64, _P, _P, _I64, _I64, _F, _F, _P]),
     "dvla_dit_sample_workspace_bytes": (C.c_int64, [_I32]),
     "dvla_dit_sample": (C.c_int, [C.POINTER(DitSampleParams), _P]),
+    "dvla_dit_sample_fm": (C.c_int, [C.POINTER(DitSampleParams), _P]),
     "dvla_dit_sample_set_stamps": (None, [_P]),
     "dvla_dit_sample_inject_timeouts": (None, [_I32]),
     "dvla_cast_f32_to_bf16": (C.c_int, [_P, _P, _I64, _P]),

@@ -33,6 +33,13 @@ __device__ __forceinline__ uint32_t pack2bf(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, b);
 }
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }  // raw v_exp_f32
+// x + a b as an fp32 multiply and an fp32 add, two roundings -- what two ATen launches compute.  hipcc contracts across the
+// __fmul_rn / __fadd_rn wrappers (plain * and + in the HIP headers) into one v_fma_f32; the pragma keeps the two operations.
+__device__ __forceinline__ float add_mul_rn(float x, float a, float b) {
+#pragma clang fp contract(off)
+  const float p = a * b;
+  return x + p;
+}
 
 // ---- fast transcendental helpers (epilogue-resident: they must cost a handful of VALU ops, not a libm call) ----
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }            // v_rcp_f32 (1 ulp)

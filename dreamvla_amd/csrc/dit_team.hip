@@ -504,7 +504,10 @@ __device__ __attribute__((noinline)) void attention_phase(const Team tm, const b
 
 // team member 0, between two sampler steps: [final LayerNorm + linear of step j - 1 -> guidance + DDIM update] -> token embedding
 // of step j.  xs: the sampler state (bs, T, C) fp32 in LDS; mo: the model output (R, 16) in LDS.
-template <int KS, int RB>
+// FM (dvla_dit_sample_fm): the flow-matching Euler update x + delta u in place of the DDIM update, coef = (steps) step sizes.  A
+// compile-time choice: the DDIM instantiation is the DDIM kernel's code as it was, instruction for instruction (a run-time branch
+// here changed how hipcc contracts the DDIM arithmetic).
+template <int KS, int RB, bool FM = false>
 __device__ __attribute__((noinline)) void step_boundary(const Team tm, const Args& a, int j) {
   DIT_LDS();
   float* mo = dit_lds + MO_OFF;
@@ -513,18 +516,25 @@ __device__ __attribute__((noinline)) void step_boundary(const Team tm, const Arg
   const int L = 2 * a.T, R = 2 * a.bs * L, per = a.T * a.C, n = a.bs * per;
   if (j > 0) {
     gemm_phase<KS, 1, RB, true, EPI_FINAL>(tm, a.final_w, a.final_b, a.C, a.X, a.D, nullptr, 0, R, a.eps);
-    const float ca = a.coef[4 * (j - 1)], cb = a.coef[4 * (j - 1) + 1], sp = a.coef[4 * (j - 1) + 2], sq = a.coef[4 * (j - 1) + 3];
+    // (flow matching reads one coefficient per step: coef holds `steps` floats there, not 4 x steps)
+    const float ca = FM ? a.coef[j - 1] : a.coef[4 * (j - 1)], cb = FM ? 0.f : a.coef[4 * (j - 1) + 1],
+                sp = FM ? 0.f : a.coef[4 * (j - 1) + 2], sq = FM ? 0.f : a.coef[4 * (j - 1) + 3];
     for (int i = t; i < n; i += 64 * NWAVES) {
       const int s = i / per, r = i - s * per, tok = r / a.C, c = r - tok * a.C;
       const float cond = mo[(s * L + a.T + tok) * 16 + c], unc = mo[((s + a.bs) * L + a.T + tok) * 16 + c];
-      // csrc/elementwise.hip ddim_cfg_step_kernel, operation by operation
+      // csrc/elementwise.hip ddim_cfg_step_kernel / fm_cfg_step_kernel, operation by operation
       const float d = bf2f(f2bf(__fsub_rn(cond, unc)));
       const float sd = bf2f(f2bf(__fmul_rn(a.cfg, d)));
       const float e = bf2f(f2bf(__fadd_rn(unc, sd)));
-      const float ax = __fmul_rn(ca, xs[i]);
-      const float px = __fsub_rn(ax, __fmul_rn(cb, e));
-      const float e2 = __fdiv_rn(__fsub_rn(ax, px), cb);
-      const float xn = __fadd_rn(__fmul_rn(px, sp), __fmul_rn(sq, e2));
+      float xn;
+      if constexpr (FM) {
+        xn = add_mul_rn(xs[i], ca, e);                           // x + delta u: multiply, then add (no FMA)
+      } else {
+        const float ax = __fmul_rn(ca, xs[i]);
+        const float px = __fsub_rn(ax, __fmul_rn(cb, e));
+        const float e2 = __fdiv_rn(__fsub_rn(ax, px), cb);
+        xn = __fadd_rn(__fmul_rn(px, sp), __fmul_rn(sq, e2));
+      }
       xs[i] = xn;
       if (j == a.steps) {
         const unsigned st = __hip_atomic_load(tm.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -568,8 +578,8 @@ __device__ __attribute__((noinline)) void step_boundary(const Team tm, const Arg
   team_arrive(tm);
 }
 
-// KS = hidden / 256 (3: DiT-B, 4: DiT-L); RB = blocks of 16 token rows
-template <int KS, int RB>
+// KS = hidden / 256 (3: DiT-B, 4: DiT-L); RB = blocks of 16 token rows; FM: the flow-matching update at the step boundary
+template <int KS, int RB, bool FM = false>
 __global__ __launch_bounds__(64 * NWAVES) void dit_team_kernel(Args a) {
   DIT_LDS();
   if ((blockIdx.x & 7) != 0) return;                 // the team: workgroups placed on XCC 0
@@ -590,7 +600,7 @@ __global__ __launch_bounds__(64 * NWAVES) void dit_team_kernel(Args a) {
     // previous exchange first: one counter serves all exchanges, so nobody may arrive twice before everybody has arrived once.
     if (tm.rank == 0) {
       const Args boundary_args = a;            // (a copy for the call: the kernel's own arguments stay in scalar registers)
-      step_boundary<KS, RB>(tm, boundary_args, j);
+      step_boundary<KS, RB, FM>(tm, boundary_args, j);
     } else if (j < a.steps) {
       if (j > 0) {
         if (wave == 0) team_wait(tm);
@@ -629,7 +639,7 @@ __global__ __launch_bounds__(64 * NWAVES) void dit_team_kernel(Args a) {
 // every L2 access of the exchange itself (the sc1 stores' acknowledgements, the counter, the operand loads) waits in the same
 // queues: stream and exchange do not overlap beyond the first microsecond, they add.  Nothing requested is ever left unconsumed (a load that lands
 // after its register was re-used would corrupt it), and no request is in flight across the only real call (step_boundary).
-template <int KS, int RB>
+template <int KS, int RB, bool FM = false>
 __global__ __launch_bounds__(64 * NWAVES) void dit_team_kernel_ahead(Args a) {
   DIT_LDS();
   if ((blockIdx.x & 7) != 0) return;
@@ -656,7 +666,7 @@ __global__ __launch_bounds__(64 * NWAVES) void dit_team_kernel_ahead(Args a) {
   for (int j = 0; j <= a.steps; ++j) {
     if (tm.rank == 0) {
       const Args boundary_args = a;            // (a copy for the call: the kernel's own arguments stay in scalar registers)
-      step_boundary<KS, RB>(tm, boundary_args, j);
+      step_boundary<KS, RB, FM>(tm, boundary_args, j);
     } else if (j < a.steps) {
       if (j > 0) {
         if (wave == 0) team_wait(tm);
@@ -735,7 +745,9 @@ extern "C" void dvla_dit_sample_set_stamps(void* buf) { g_dit_stamps = reinterpr
 static int g_dit_inject = 0;
 extern "C" void dvla_dit_sample_inject_timeouts(int32_t n) { g_dit_inject = n > 0 ? n : 0; }
 
-extern "C" int dvla_dit_sample(const dvla_dit_sample_params* q, void* stream_) {
+// fm = 0: dvla_dit_sample (DDIM), 1: dvla_dit_sample_fm (flow-matching Euler steps) -- one launch path, the kernel templates
+// instantiated for each update
+static int dit_sample_launch(const dvla_dit_sample_params* q, int fm, void* stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (!q || !q->blocks || !q->xemb_w || !q->xemb_b || !q->final_w || !q->final_b || !q->pos || !q->cond || !q->coef || !q->noise ||
       !q->out || !q->workspace)
@@ -777,13 +789,23 @@ extern "C" int dvla_dit_sample(const dvla_dit_sample_params* q, void* stream_) {
   if (ahead < 0) { const char* e = getenv("DVLA_DIT_AHEAD"); ahead = e ? atoi(e) : 1; }      // 0: the call-per-phase kernel (A/B)
   static bool attr_set = false;
   if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)dit_team_kernel_ahead<KS, RB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)dit_team_kernel<KS, RB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)dit_team_kernel_ahead<KS, RB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+        hipFuncSetAttribute((const void*)dit_team_kernel<KS, RB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+        hipFuncSetAttribute((const void*)dit_team_kernel_ahead<KS, RB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+        hipFuncSetAttribute((const void*)dit_team_kernel<KS, RB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
       return DVLA_ERR_LAUNCH;
     attr_set = true;
   }
   const dim3 grid((unsigned)(8 * TEAM)), block(64 * NWAVES);
-  if (ahead) hipLaunchKernelGGL((dit_team_kernel_ahead<KS, RB>), grid, block, lds, stream, a);
-  else hipLaunchKernelGGL((dit_team_kernel<KS, RB>), grid, block, lds, stream, a);
+  if (fm) {
+    if (ahead) hipLaunchKernelGGL((dit_team_kernel_ahead<KS, RB, true>), grid, block, lds, stream, a);
+    else hipLaunchKernelGGL((dit_team_kernel<KS, RB, true>), grid, block, lds, stream, a);
+  } else {
+    if (ahead) hipLaunchKernelGGL((dit_team_kernel_ahead<KS, RB, false>), grid, block, lds, stream, a);
+    else hipLaunchKernelGGL((dit_team_kernel<KS, RB, false>), grid, block, lds, stream, a);
+  }
   return dvla_check_launch();
 }
+
+extern "C" int dvla_dit_sample(const dvla_dit_sample_params* q, void* stream) { return dit_sample_launch(q, 0, stream); }
+extern "C" int dvla_dit_sample_fm(const dvla_dit_sample_params* q, void* stream) { return dit_sample_launch(q, 1, stream); }

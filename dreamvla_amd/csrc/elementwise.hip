@@ -333,6 +333,32 @@ extern "C" int dvla_ddim_cfg_step(const void* model_out, int64_t sample_stride, 
   return dvla_check_launch();
 }
 
+// classifier-free guidance + one Euler step of the flow-matching sampler (dvla.h): the guidance exactly as ddim_cfg_step_kernel
+// (three bf16 roundings), then x + delta * u in fp32 as two operations (add_mul_rn) -- the ATen expression multiplies and adds in
+// two launches
+__global__ void fm_cfg_step_kernel(const bf16_t* __restrict__ mo, int64_t sample_stride, const float* __restrict__ x,
+                                   float* __restrict__ xn, int64_t bs, int64_t per, float cfg, float delta) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= bs * per) return;
+  const int64_t s = i / per, j = i - s * per;
+  const float cond = bf2f(mo[s * sample_stride + j]), unc = bf2f(mo[(s + bs) * sample_stride + j]);
+  const float d = bf2f(f2bf(__fsub_rn(cond, unc)));
+  const float sd = bf2f(f2bf(__fmul_rn(cfg, d)));
+  const float u = bf2f(f2bf(__fadd_rn(unc, sd)));
+  xn[i] = add_mul_rn(x[i], delta, u);
+}
+
+extern "C" int dvla_fm_cfg_step(const void* model_out, int64_t sample_stride, const float* x, float* x_next, int64_t bs,
+                                int64_t per_sample, float cfg_scale, float delta, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (!model_out || !x || !x_next || bs < 0 || per_sample <= 0 || sample_stride < per_sample) return DVLA_ERR_ARG;
+  if (bs == 0) return DVLA_OK;
+  const int64_t n = bs * per_sample;
+  hipLaunchKernelGGL(fm_cfg_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                     reinterpret_cast<const bf16_t*>(model_out), sample_stride, x, x_next, bs, per_sample, cfg_scale, delta);
+  return dvla_check_launch();
+}
+
 extern "C" int dvla_act_fwd(const void* x, void* y, int64_t n, int32_t act, void* stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (!x || !y || n < 0) return DVLA_ERR_ARG;

@@ -645,6 +645,13 @@ class DreamVLA(nn.Module):
                     # the same sampler with the step-invariant work hoisted and the per-step algebra in one kernel
                     # (ActionModel.sample_ddim_cfg; `model.fast_sampler = False` runs the operation-by-operation loop below)
                     samples = self.action_model.sample_ddim_cfg(cond, noise[:bs].float(), cfg_scale)
+                elif getattr(self, "fast_sampler", True) and hasattr(self.action_model, "sample_fm_cfg"):
+                    # flow matching (ActionModelFM.sample_fm_cfg): the Euler loop of FMDiffusion with the same hoisting and one
+                    # kernel per step.  Its start noise is test_noise, or -- as FMDiffusion draws it -- a fresh (2 bs, T, C)
+                    # float32 draw whose first half the guided loop integrates (the same values and the same generator use)
+                    start = (noise[:bs].float() if test_noise is not None
+                             else torch.randn(noise.shape, device=cond.device)[:bs].contiguous())
+                    samples = self.action_model.sample_fm_cfg(cond, start, cfg_scale)
                 else:
                     samples = self.action_model.ddim_diffusion.ddim_sample_loop(
                         self.action_model.net.forward_with_cfg, noise.shape, noise, clip_denoised=False,

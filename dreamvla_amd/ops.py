@@ -574,6 +574,23 @@ def ddim_cfg_step(model_out, x, cfg_scale, a, b, sqrt_acp_prev, sqrt_1m_acp_prev
     return out
 
 
+def fm_cfg_step(model_out, x, cfg_scale, delta):
+    """classifier-free guidance + one Euler step of the flow-matching sampler in one launch (dvla_fm_cfg_step): what
+    forward_with_cfg's guidance and FMDiffusion's `final + delta * ut.to(fp32)` compute, with the same rounding points.
+    model_out: bf16 (2 bs, T, C) -- a view whose samples are contiguous (e.g. `full[:, T:, :]`); x: fp32 (bs, T, C)."""
+    lib = _lib.load()
+    _req(model_out, "fm_cfg_step.model_out")
+    bs, per = x.shape[0], x[0].numel()
+    if model_out.shape[0] != 2 * bs or model_out[0].numel() != per or model_out.dtype != BF16 or x.dtype != torch.float32:
+        raise ValueError("fm_cfg_step: model_out (2 bs, ...) bf16 and x (bs, ...) fp32 of matching sample size")
+    if not model_out[0].is_contiguous() or (bs > 0 and model_out.stride(0) < per) or not x.is_contiguous():
+        raise ValueError("fm_cfg_step: samples must be contiguous")
+    out = torch.empty_like(x)
+    check(lib.dvla_fm_cfg_step(model_out.data_ptr(), int(model_out.stride(0)), x.data_ptr(), out.data_ptr(), bs, per,
+                               float(cfg_scale), float(delta), _stream()), "dvla_fm_cfg_step")
+    return out
+
+
 # The whole evaluation sampler of the DiT head in one launch (csrc/dit_team.hip, include/dvla.h dvla_dit_sample)
 DIT_TEAM = os.environ.get("DVLA_DIT_TEAM", "1") != "0"        # 0: always the launch-by-launch sampler (measurement / A-B)
 _DIT_TEAM_CUS = {}
@@ -619,9 +636,10 @@ def dit_team_inject_timeouts(n):
 
 
 def dit_team_sample(block_ptrs, depth, hidden, heads, xemb_w, xemb_b, final_w, final_b, pos, cond, coef, noise, cfg_scale, ln_eps,
-                    workspace):
+                    workspace, fm=False):
     """block_ptrs: int64 device tensor (depth, 8) of bf16 weight addresses (qkv w, b, proj w, b, fc1 w, b, fc2 w, b);
-    cond (steps, 2 bs, T, hidden) bf16; coef (steps, 4) fp32; noise (bs, T, C) fp32.  Returns the samples (bs, T, C) fp32."""
+    cond (steps, 2 bs, T, hidden) bf16; coef (steps, 4) fp32 -- with fm=True (dvla_dit_sample_fm: the flow-matching Euler
+    update) (steps,) fp32, the step size of each step; noise (bs, T, C) fp32.  Returns the samples (bs, T, C) fp32."""
     lib = _lib.load()
     for t, nm in ((xemb_w, "xemb_w"), (xemb_b, "xemb_b"), (final_w, "final_w"), (final_b, "final_b"), (pos, "pos"), (cond, "cond")):
         _req(t, "dit_team_sample." + nm)
@@ -631,7 +649,7 @@ def dit_team_sample(block_ptrs, depth, hidden, heads, xemb_w, xemb_b, final_w, f
         raise ValueError("dit_team_sample: coef / noise contiguous fp32")
     steps, two_bs, T = cond.shape[0], cond.shape[1], cond.shape[2]
     bs, Cn = noise.shape[0], noise.shape[2]
-    if two_bs != 2 * bs or noise.shape[1] != T or tuple(coef.shape) != (steps, 4) or tuple(block_ptrs.shape) != (depth, 8):
+    if two_bs != 2 * bs or noise.shape[1] != T or tuple(coef.shape) != ((steps,) if fm else (steps, 4)) or tuple(block_ptrs.shape) != (depth, 8):
         raise ValueError("dit_team_sample: shapes")
     out = torch.empty_like(noise)
     p = _lib.DitSampleParams()
@@ -641,7 +659,10 @@ def dit_team_sample(block_ptrs, depth, hidden, heads, xemb_w, xemb_b, final_w, f
     p.workspace, p.workspace_bytes = workspace.data_ptr(), workspace.numel()
     p.cfg_scale, p.ln_eps = float(cfg_scale), float(ln_eps)
     p.depth, p.hidden, p.heads, p.channels, p.tokens, p.bs, p.steps = int(depth), int(hidden), int(heads), int(Cn), int(T), int(bs), int(steps)
-    check(lib.dvla_dit_sample(C.byref(p), _stream()), "dvla_dit_sample")
+    if fm:
+        check(lib.dvla_dit_sample_fm(C.byref(p), _stream()), "dvla_dit_sample_fm")
+    else:
+        check(lib.dvla_dit_sample(C.byref(p), _stream()), "dvla_dit_sample")
     return out
 
 

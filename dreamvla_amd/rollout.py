@@ -118,6 +118,7 @@ class RolloutEngine:
         self._team_allowed = True
         self._team_in_decode = False
         self._team_seen = None
+        self._team_entry = None                 # the sampler cache entry (workspace) the decode's team launch used
 
     # ------------------------------------------------------------------------------------------------------------
     def reset(self, mask=None):
@@ -197,6 +198,8 @@ class RolloutEngine:
                 am.team_sampler = shared
                 # (an eager call, or the capture of this engine's graph: what it launched is what its replays launch)
                 self._team_in_decode = getattr(am, "team_launches", 0) > before
+                if self._team_in_decode:          # the workspace of the launch just made (DDIM or flow matching, any step count)
+                    self._team_entry = getattr(am, "team_entry", None)
         return out[0], out[1]
 
     @torch.no_grad()
@@ -289,17 +292,15 @@ class RolloutEngine:
 
     def _team_sampler_in_use(self):
         """did THIS engine's decode path (eager, or its captured graph) launch the persistent sampler kernel?  Recorded by
-        `_decode_eager` whenever the decode runs in Python (`ActionModel.sample_ddim_cfg` counts its team launches; the shapes
-        that take the kernel are decided there: one episode, DiT-B)"""
+        `_decode_eager` whenever the decode runs in Python (`ActionModel.sample_ddim_cfg` and `ActionModelFM.sample_fm_cfg` count
+        their team launches; the shapes that take the kernel are decided there: one episode, DiT-B)"""
         return bool(self.needs_noise and self._team_in_decode)
 
     def _team_status(self):
-        """the sampler workspace's cache entry of the action model (None before the first team launch)"""
-        am = getattr(self.model, "action_model", None)
-        for k, v in (getattr(am, "_fast_tables", None) or {}).items():
-            if isinstance(k, tuple) and k and k[0] == "team" and k[1] == str(self.device):
-                return v
-        return None
+        """the action model's sampler cache entry -- workspace, last timeout count seen -- that THIS engine's decode launched the
+        kernel on (recorded by `_decode_eager`; None before the first team launch).  Not a lookup by device: a model that has
+        sampled with two timestep counts, or with both samplers, has one workspace each (round-6 ADVICE)."""
+        return self._team_entry
 
     def _team_timed_out(self):
         """has the kernel's timeout count (word 33 of its workspace: include/dvla.h) moved since this engine last looked?"""
@@ -320,7 +321,7 @@ class RolloutEngine:
         self.team_fallbacks += 1
         if self.use_graph:                       # the captured decode contains the team kernel: warm up and capture again
             self._decode_g = _Graphed(self._decode_eager, self.warmup_decodes)
-        warnings.warn("RolloutEngine: dvla_dit_sample timed out (the GPU is shared or busy: its 32 workgroups were not co-resident); "
+        warnings.warn("RolloutEngine: the one-XCD sampler kernel timed out (the GPU is shared or busy: its 32 workgroups were not co-resident); "
                       "this engine now runs the launch-by-launch sampler", RuntimeWarning)
 
 

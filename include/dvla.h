@@ -260,6 +260,12 @@ int dvla_act_fwd(const void* x, void* y, int64_t n, int32_t act, void* stream);
  * model_out + (bs + i) * sample_stride, per_sample contiguous values each; x, x_next: fp32 (bs, per_sample) contiguous. */
 int dvla_ddim_cfg_step(const void* model_out, int64_t sample_stride, const float* x, float* x_next, int64_t bs, int64_t per_sample,
                        float cfg_scale, float a, float b, float sqrt_acp_prev, float sqrt_1m_acp_prev, void* stream);
+/* One step of the flow-matching head's evaluation sampler (models/action_model/respace.py:118-191 FMDiffusion over
+ * forward_with_cfg): the same guidance as dvla_ddim_cfg_step (three bf16 roundings) followed by the Euler update
+ *     x_next = x + delta u
+ * in fp32, one multiply and one add (no contraction).  Arguments and layouts as dvla_ddim_cfg_step. */
+int dvla_fm_cfg_step(const void* model_out, int64_t sample_stride, const float* x, float* x_next, int64_t bs, int64_t per_sample,
+                     float cfg_scale, float delta, void* stream);
 /* The WHOLE evaluation sampler of the DiT action head in one launch (models/dreamvla_model.py:935-987: ddim_sample_loop over
  * net.forward_with_cfg, eta = 0; models/action_model/models.py:162-268 DiT.forward / forward_with_cfg; gaussian_diffusion.py:
  * 522-569 ddim_sample): `steps` x { token embedding, `depth` DiT blocks, final layer, guidance + DDIM update } on 2 bs sequences
@@ -297,6 +303,13 @@ typedef struct dvla_dit_sample_params {
 } dvla_dit_sample_params;
 int64_t dvla_dit_sample_workspace_bytes(int32_t hidden);
 int dvla_dit_sample(const dvla_dit_sample_params* p, void* stream);
+/* The flow-matching head's evaluation sampler (FMDiffusion over forward_with_cfg: models/action_model/respace.py:118-191) as the
+ * same persistent kernel: the same exchange schedule, shape gate, workspace, timeout contract (word 33 / 34, NaN output, the
+ * launch retires its own status) and test hooks as dvla_dit_sample, with the Euler update of dvla_fm_cfg_step in place of the
+ * DDIM update.  The fields of p mean what they mean there, except
+ *   cond       (steps, 2 bs, tokens, hidden) bf16: z_embedder([cond ; uncondition]) + t_embedder(j / steps), j = 0 the first step
+ *   coef       (steps) fp32 on the device: the Euler step size delta of each sampler step (1 / steps upstream) */
+int dvla_dit_sample_fm(const dvla_dit_sample_params* p, void* stream);
 /* measurement: a device buffer of 2 x 8 x (steps x (1 + 5 depth) + 1) uint64 that later launches fill with wall-clock stamps
  * (100 MHz) of team members 0 and 17 -- per exchange: weights requested, producers arrived, operands landed, partial tiles in
  * LDS, results stored; NULL (the default) switches it off */
