@@ -361,6 +361,62 @@ class DreamVLA(nn.Module):
             self.action_decoder_type = next(self.action_decoder.parameters()).type()
 
     # ------------------------------------------------------------------------------------------------
+    def dream_names(self):
+        """the dream heads this model was built with, in the order of their query tokens"""
+        have = (("image", "obs_pred"), ("depth", "depth_pred"), ("dino", "dino_feat_pred"), ("sam", "sam_feat_pred"),
+                ("traj", "trajectory_pred"))
+        return tuple(k for k, flag in have if getattr(self, flag, False))
+
+    def _check_dreams(self, dreams):
+        if dreams is None:
+            return ()
+        if isinstance(dreams, str):
+            dreams = (dreams,)
+        want = tuple(dict.fromkeys(dreams))
+        for k in want:
+            if k not in ops.DREAM_KINDS:
+                raise ValueError(f"dreams: {k!r} is not one of {ops.DREAM_KINDS}")
+            if k not in DreamVLA.dream_names(self):
+                raise ValueError(f"dreams: this model was built without the {k!r} head (it has {DreamVLA.dream_names(self)})")
+        return want
+
+    def _dream_heads(self):
+        """(name, first query row, rows, first column, end column, queries per view, mask tokens, projector, mask token, position
+        table, decoder, norm, prediction layer, activation) of every head the model has; query rows are counted from the first
+        prediction query of a frame (dreamvla_model.py:793-911: with share_query every head reads its quarter of the columns
+        of the shared rows)"""
+        H, sq = self.hidden_dim, self.share_query
+        heads, cur = [], 0
+        if self.obs_pred:
+            heads.append(("image", cur, self.NUM_OBS_TOKEN, 0, int(H / 4) if sq else H, self.NUM_OBS_TOKEN_PER_IMAGE,
+                          self.NUM_MASK_TOKEN, self.image_decoder_obs_pred_projector, self.mask_token,
+                          self.image_decoder_position_embedding, self.image_decoder, self.image_decoder_norm,
+                          self.image_decoder_pred, "none"))
+            cur = 0 if sq else cur + self.NUM_OBS_TOKEN
+        if self.depth_pred:
+            heads.append(("depth", cur, self.NUM_DEPTH_TOKEN, int(H / 4) if sq else 0, int(H / 2) if sq else H,
+                          self.NUM_OBS_TOKEN_PER_DEPTH, self.NUM_DEPTH_MASK_TOKEN, self.depth_decoder_obs_pred_projector,
+                          self.depth_mask_token, self.depth_decoder_position_embedding, self.depth_decoder,
+                          self.depth_decoder_norm, self.depth_decoder_pred, "relu"))
+            cur = 0 if sq else cur + self.NUM_DEPTH_TOKEN
+        if self.dino_feat_pred:
+            heads.append(("dino", cur, self.NUM_DINO_TOKEN, int(H / 2) if sq else 0, int(H * 3 / 4) if sq else H,
+                          self.NUM_OBS_TOKEN_PER_DINO, self.NUM_DINO_MASK_TOKEN, self.dino_decoder_obs_pred_projector,
+                          self.dino_mask_token, self.dino_decoder_position_embedding, self.dino_feat_decoder,
+                          self.dino_decoder_norm, self.dino_decoder_pred, "none"))
+            cur = 0 if sq else cur + self.NUM_DINO_TOKEN
+        if self.sam_feat_pred:
+            heads.append(("sam", cur, self.NUM_SAM_TOKEN, int(H * 3 / 4) if sq else 0, H, self.NUM_OBS_TOKEN_PER_SAM,
+                          self.NUM_SAM_MASK_TOKEN, self.sam_decoder_obs_pred_projector, self.sam_mask_token,
+                          self.sam_decoder_position_embedding, self.sam_feat_decoder, self.sam_decoder_norm,
+                          self.sam_decoder_pred, "none"))
+            cur = 0 if sq else cur + self.NUM_SAM_TOKEN
+        if self.trajectory_pred:
+            heads.append(("traj", cur, self.NUM_TRAJ_TOKEN, 0, H, self.NUM_OBS_TOKEN_PER_TRAJ, self.NUM_TRAJ_MASK_TOKEN,
+                          self.traj_decoder_obs_pred_projector, self.traj_mask_token, self.traj_decoder_position_embedding,
+                          self.traj_decoder, self.traj_decoder_norm, self.traj_decoder_pred, "none"))
+        return heads
+
     def _dream_head(self, feat, n2, n_q, n_mask, projector, mask_token, pos, decoder, norm, pred, act="none"):
         """feat: (B, S, n_tok, Hin) slice of the trunk output -> pred (n2*n_mask, out).  dreamvla_model.py:793-911."""
         Hd = self.hidden_dim
@@ -488,7 +544,7 @@ class DreamVLA(nn.Module):
 
         return [text_embedding, state_embedding, image_primary_embedding, image_wrist_embedding, cls_primary, cls_wrist]
 
-    def decode_tokens(self, parts, action_label=None, mode='train', test_noise=None, test_select=None):
+    def decode_tokens(self, parts, action_label=None, mode='train', test_noise=None, test_select=None, dreams=None):
         """Token assembly with the prediction queries, trunk, dream heads (train) and action head
         (dreamvla_model.py:739-991).  `parts`: the list from `encode_frames`, or one (B, S, 36, H) tensor of them.
         `test_noise` (B*S, action_pred_steps, 7), mode='test' with the DiT head only: the sampler's start noise as an INPUT
@@ -497,7 +553,13 @@ class DreamVLA(nn.Module):
         `test_select` (B,) int64 on the device, mode='test' with the DiT head only: sample the action of ONE window position
         per sequence (the position the evaluation wrapper executes, utils/eval_utils_calvin.py:141-146) instead of all S --
         the sampler's batch elements are independent, so the selected position's samples are those of the full call from the
-        same noise rows; the action outputs are then (1, B, steps, .) and `test_noise` is (B, steps, 7)."""
+        same noise rows; the action outputs are then (1, B, steps, .) and `test_noise` is (B, steps, 7).
+        `dreams`, mode='test' only (an addition: the reference decodes its dreams in mode='train' only): None, or names out of
+        {"image", "depth", "dino", "sam", "traj"} -- the matching slots of the returned tuple then carry that head's prediction
+        instead of None, computed under no_grad on the kernels of the training path: every window position, shaped as in train
+        mode (B*S, views, pred_num, rows, cols), or with `test_select` (any action head) the selected position only, (B, views,
+        ...).  A head the model was not built with raises ValueError.  The action outputs do not depend on `dreams`."""
+        want = self._check_dreams(dreams) if mode != 'train' else ()
         if torch.is_tensor(parts):
             parts = [parts]
         else:
@@ -536,71 +598,36 @@ class DreamVLA(nn.Module):
                                                        mask_tables=getattr(self, "_step_mask_tables", None))
         transformer_output = transformer_output.view(B, S, -1, H)
 
-        # dream heads (training only)                                                        (792-911)
+        # dream heads: training -- and, for the heads named in `dreams`, evaluation                  (792-911)
         q0 = pred_token_start_idx
-        cur = 0
-        n2 = n * 2
-        if self.obs_pred and mode == 'train':
-            if self.share_query:
-                feat = transformer_output[:, :, q0:q0 + self.NUM_OBS_TOKEN, :int(H / 4)]
-                cur = 0
-            else:
-                feat = transformer_output[:, :, q0:q0 + self.NUM_OBS_TOKEN, :]
-                cur += self.NUM_OBS_TOKEN
-            p = self._dream_head(feat, n2, self.NUM_OBS_TOKEN_PER_IMAGE, self.NUM_MASK_TOKEN,
-                                 self.image_decoder_obs_pred_projector, self.mask_token,
-                                 self.image_decoder_position_embedding, self.image_decoder, self.image_decoder_norm,
-                                 self.image_decoder_pred)
-            image_pred = p.view(n, self.NUM_OBS_TOKEN // self.NUM_OBS_TOKEN_PER_IMAGE, self.pred_num,
-                                self.NUM_MASK_TOKEN // self.pred_num, -1)
-        if self.depth_pred and mode == 'train':
-            if self.share_query:
-                feat = transformer_output[:, :, q0 + cur:q0 + cur + self.NUM_DEPTH_TOKEN, int(H / 4):int(H / 2)]
-                cur = 0
-            else:
-                feat = transformer_output[:, :, q0 + cur:q0 + cur + self.NUM_DEPTH_TOKEN, :]
-                cur += self.NUM_DEPTH_TOKEN
-            p = self._dream_head(feat, n2, self.NUM_OBS_TOKEN_PER_DEPTH, self.NUM_DEPTH_MASK_TOKEN,
-                                 self.depth_decoder_obs_pred_projector, self.depth_mask_token,
-                                 self.depth_decoder_position_embedding, self.depth_decoder, self.depth_decoder_norm,
-                                 self.depth_decoder_pred, act="relu")
-            depth_pred = p.view(n, self.NUM_DEPTH_TOKEN // self.NUM_OBS_TOKEN_PER_DEPTH, self.pred_num,
-                                self.NUM_DEPTH_MASK_TOKEN // self.pred_num, -1)
-        if self.dino_feat_pred and mode == 'train':
-            if self.share_query:
-                feat = transformer_output[:, :, q0 + cur:q0 + cur + self.NUM_DINO_TOKEN, int(H / 2):int(H * 3 / 4)]
-                cur = 0
-            else:
-                feat = transformer_output[:, :, q0 + cur:q0 + cur + self.NUM_DINO_TOKEN, :]
-                cur += self.NUM_DINO_TOKEN
-            p = self._dream_head(feat, n2, self.NUM_OBS_TOKEN_PER_DINO, self.NUM_DINO_MASK_TOKEN,
-                                 self.dino_decoder_obs_pred_projector, self.dino_mask_token,
-                                 self.dino_decoder_position_embedding, self.dino_feat_decoder, self.dino_decoder_norm,
-                                 self.dino_decoder_pred)
-            dino_pred = p.view(n, self.NUM_DINO_TOKEN // self.NUM_OBS_TOKEN_PER_DINO, self.pred_num,
-                               self.NUM_DINO_MASK_TOKEN // self.pred_num, -1)
-        if self.sam_feat_pred and mode == 'train':
-            if self.share_query:
-                feat = transformer_output[:, :, q0 + cur:q0 + cur + self.NUM_SAM_TOKEN, int(H * 3 / 4):int(H)]
-                cur = 0
-            else:
-                feat = transformer_output[:, :, q0 + cur:q0 + cur + self.NUM_SAM_TOKEN, :]
-                cur += self.NUM_SAM_TOKEN
-            p = self._dream_head(feat, n2, self.NUM_OBS_TOKEN_PER_SAM, self.NUM_SAM_MASK_TOKEN,
-                                 self.sam_decoder_obs_pred_projector, self.sam_mask_token,
-                                 self.sam_decoder_position_embedding, self.sam_feat_decoder, self.sam_decoder_norm,
-                                 self.sam_decoder_pred)
-            sam_pred = p.view(n, self.NUM_SAM_TOKEN // self.NUM_OBS_TOKEN_PER_SAM, self.pred_num,
-                              self.NUM_SAM_MASK_TOKEN // self.pred_num, -1)
-        if self.trajectory_pred and mode == 'train':
-            feat = transformer_output[:, :, q0 + cur:q0 + cur + self.NUM_TRAJ_TOKEN, :]
-            ntv = self.NUM_TRAJ_TOKEN // self.NUM_OBS_TOKEN_PER_TRAJ
-            p = self._dream_head(feat, n * ntv, self.NUM_OBS_TOKEN_PER_TRAJ, self.NUM_TRAJ_MASK_TOKEN,
-                                 self.traj_decoder_obs_pred_projector, self.traj_mask_token,
-                                 self.traj_decoder_position_embedding, self.traj_decoder, self.traj_decoder_norm,
-                                 self.traj_decoder_pred)
-            traj_pred = p.view(n, ntv, self.pred_num, self.NUM_TRAJ_MASK_TOKEN // self.pred_num, -1)
-            cur += self.NUM_TRAJ_TOKEN
+        outs = {}
+        if mode == 'train' or want:
+            gathered = None
+            if mode != 'train' and test_select is not None:
+                if tuple(test_select.shape) != (B,):
+                    raise ValueError(f"test_select {tuple(test_select.shape)}: expected ({B},)")
+                # the executed position's query rows, read out of the trunk output in place: the decoders then run on 2 B
+                # sequences instead of 2 B S
+                gathered = ops.gather_positions(transformer_output, test_select, q0, self._num_query_tokens()).unsqueeze(1)
+            for (name, start, ntok, c0, c1, n_q, n_mask, projector, mask_token, pos, decoder, norm, pred, act) in self._dream_heads():
+                if mode != 'train' and name not in want:
+                    continue
+                if gathered is not None:
+                    feat, nseq = gathered[:, :, start:start + ntok, c0:c1], B
+                else:
+                    feat, nseq = transformer_output[:, :, q0 + start:q0 + start + ntok, c0:c1], n
+                views = ntok // n_q
+                if mode == 'train':
+                    p_ = self._dream_head(feat, nseq * views, n_q, n_mask, projector, mask_token, pos, decoder, norm, pred, act=act)
+                else:
+                    # a few hundred to a few thousand rows (2 B x 205 / 265): no timed tuner trials on launches of microseconds --
+                    # the locked choice of a larger run, or the library's own pick (the few-rows kernel up to 512 rows)
+                    small = nseq * views * (n_q + n_mask) <= ops.DREAM_TUNE_MIN_ROWS
+                    with torch.no_grad(), ops.gemm_trials(not small):
+                        p_ = self._dream_head(feat, nseq * views, n_q, n_mask, projector, mask_token, pos, decoder, norm, pred, act=act)
+                outs[name] = p_.view(nseq, views, self.pred_num, n_mask // self.pred_num, -1)
+        image_pred, depth_pred, dino_pred = outs.get("image"), outs.get("depth"), outs.get("dino")
+        sam_pred, traj_pred = outs.get("sam"), outs.get("traj")
 
         # action head                                                                        (915-987)
         if self.action_pred_steps > 0:

@@ -2032,3 +2032,90 @@ class _MaeLoss(torch.autograd.Function):
 def mae_loss(pred, imgs, mask, patch, norm_pix=False):
     """sum(mask * mean_P((pred - patchify(imgs))^2)) / sum(mask) (norm_pix: per-patch normalised target)"""
     return _MaeLoss.apply(to_compute(pred), imgs, mask, int(patch), bool(norm_pix))
+
+
+# ---------------------------------------------------------------------------------------------------
+# dreams at evaluation (csrc/dream.hip): the executed position's query rows, and the heads' patch predictions as frames
+# ---------------------------------------------------------------------------------------------------
+DREAM_KINDS = ("image", "depth", "dino", "sam", "traj")
+
+
+DREAM_TUNE_MIN_ROWS = 4096      # dream-head decoders at evaluation below this many rows are not handed to the tuner's trials
+
+
+class gemm_trials:
+    """`with gemm_trials(False):` GEMMs inside take their locked configuration, or the library's own choice -- no timed trials
+    (GemmTuner.frozen for the duration); `gemm_trials(True)` changes nothing."""
+
+    def __init__(self, on):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.was = GemmTuner.frozen
+        if not self.on:
+            GemmTuner.frozen = True
+        return self
+
+    def __exit__(self, *exc):
+        GemmTuner.frozen = self.was
+        return False
+
+
+def gather_positions(x, sel, tok_begin, tok_count):
+    """x (B, S, T, H) bf16, sel (B,) int64 on the device -> (B, tok_count, H) = x[b, sel[b], tok_begin : tok_begin + tok_count]:
+    the rows of one window position per sequence, read out of x in place (no host read of `sel`; inference only)"""
+    lib = _lib.load()
+    _req(x, "gather_positions.x")
+    _req(sel, "gather_positions.sel", torch.int64)
+    if x.dim() != 4 or tuple(sel.shape) != (x.shape[0],):
+        raise ValueError("gather_positions: x (B, S, T, H) and sel (B,)")
+    x, sel = x.contiguous(), sel.contiguous()
+    B, S, T, H = x.shape
+    out = torch.empty((B, int(tok_count), H), dtype=BF16, device=x.device)
+    check(lib.dvla_gather_positions(x.data_ptr(), sel.data_ptr(), out.data_ptr(), B, S, T, H, int(tok_begin), int(tok_count),
+                                    _stream()), "dvla_gather_positions")
+    return out
+
+
+def dream_render(pred, kind, current=None, patch=16):
+    """A dream head's prediction as something to look at (one HIP launch; the reference has only wandb pictures of training batches).
+    kind="image": pred (n, grid^2, patch^2 * 3) bf16 in the reference's patch layout.
+        current (n, 3, patch * grid, patch * grid) bf16 = the model's own CLIP-normalised input frame of that position and view
+        -> uint8 HWC (n, H, W, 3): the per-patch normalisation of the head's target inverted with the statistics of the same
+        patch of `current`, CLIP's Normalize inverted, [0, 1] -> 0..255;
+        current=None -> float32 (n, 3, H, W): the un-patchified prediction in the normalised space the head was trained in.
+    kind="depth": pred (n, grid^2, patch^2) -> float32 (n, H, W), un-patchify only.
+    kind "dino" / "sam" / "traj": feature / track predictions have no picture; handed back as they are."""
+    if kind not in DREAM_KINDS:
+        raise ValueError(f"dream_render: kind {kind!r} is not one of {DREAM_KINDS}")
+    if kind not in ("image", "depth"):
+        return pred
+    from .preprocess import CLIP_MEAN, CLIP_STD
+    lib = _lib.load()
+    _req(pred, "dream_render.pred")
+    if pred.dim() != 3:
+        raise ValueError("dream_render: pred (n, patches, values per patch)")
+    n, L, D = pred.shape
+    grid = int(round(L ** 0.5))
+    ch = 3 if kind == "image" else 1
+    if grid * grid != L or D != patch * patch * ch:
+        raise ValueError(f"dream_render: {kind} prediction {tuple(pred.shape)} is not (n, grid^2, {patch}^2 * {ch})")
+    pred = pred.contiguous()
+    side = patch * grid
+    m3 = s3 = cur = None
+    if kind == "image" and current is not None:
+        cur = _req(current, "dream_render.current").contiguous()
+        if tuple(cur.shape) != (n, 3, side, side):
+            raise ValueError(f"dream_render: current {tuple(cur.shape)}, expected {(n, 3, side, side)}")
+        m3 = (C.c_float * 3)(*CLIP_MEAN)
+        s3 = (C.c_float * 3)(*CLIP_STD)
+        out = torch.empty((n, side, side, 3), dtype=torch.uint8, device=pred.device)
+    elif current is not None:
+        raise ValueError("dream_render: `current` belongs to kind=\"image\"")
+    elif kind == "image":
+        out = torch.empty((n, 3, side, side), dtype=torch.float32, device=pred.device)
+    else:
+        out = torch.empty((n, side, side), dtype=torch.float32, device=pred.device)
+    check(lib.dvla_dream_render(pred.data_ptr(), _ptr(cur), out.data_ptr(), n, grid, grid, int(patch), ch, m3, s3, _stream()),
+          "dvla_dream_render")
+    return out

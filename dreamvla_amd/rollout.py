@@ -18,6 +18,10 @@ over independent episodes) and removes the redundant work:
     ctypes kernel launches go to torch's current stream, which is the capture stream) and replayed per step: ~1 700
     kernel launches of a few microseconds each at B = 1 are launch-bound otherwise.
 
+  * dreams (opt-in, `dreams=`; an addition -- the reference decodes them in mode="train" only): the decode also runs the requested
+    dream heads on the executed position's query rows, which the trunk computes anyway, and renders them (csrc/dream.hip);
+    `last_dreams` holds the frame the policy expects next, its depth map and its feature predictions for every control step.
+
 Episodes of one batch advance in lock-step (one `step` = one control step of every episode); `reset(mask)` restarts
 the episodes selected by a boolean mask (their history is cleared, the others keep theirs).
 """
@@ -73,7 +77,8 @@ class _Graphed:
 
 
 class RolloutEngine:
-    def __init__(self, model, batch_size, history_len=None, use_graph=True, warmup_decodes=3, sample="newest", text="latched"):
+    def __init__(self, model, batch_size, history_len=None, use_graph=True, warmup_decodes=3, sample="newest", text="latched",
+                 dreams=()):
         self.model = model.module if hasattr(model, "module") else model
         m = self.model
         if m.training:
@@ -98,6 +103,16 @@ class RolloutEngine:
         # sampler's batch elements are independent, so "newest" -- DDIM over B rows instead of B * S -- returns the same
         # executed action from the same noise row; "all" keeps the reference's (B, S, steps, .) action outputs.
         self.sample_all = (sample == "all") or not self.needs_noise
+        # Dreams (an addition: the reference decodes them in mode="train" only).  `dreams`: names out of ops.DREAM_KINDS that the
+        # model has a head for.  The decode -- eager or the captured graph -- then also runs those heads on the executed position's
+        # query rows ("newest"; all S positions with sample="all") and the render kernel (ops.dream_render; the image against the
+        # real frame of that position, which the engine keeps next to the token ring: 2 views x 301 KB per episode, x S with
+        # "all").  `step` returns what it returns without them; the dreams of the last step are in `last_dreams`.
+        from .dreamvla_model import DreamVLA
+        self.dreams = DreamVLA._check_dreams(m, dreams)
+        self.dreams_all = (sample == "all")
+        self.last_dreams = {}
+        self.frames = None                      # newest real frame (B, 2, 3, h, w), or the window's (B, S, 2, 3, h, w) with "all"
         # Instruction text.  "latched" = the wrapper's semantics, literally (eval_utils_calvin.py:109-112: `text_queue` is filled
         # once, when it is empty -- i.e. at the first step after `reset()` -- and kept): an episode's instruction is the one it was
         # given at its first step after a reset; a different `text_token` row later is ignored until the next reset.  "current" =
@@ -159,18 +174,26 @@ class RolloutEngine:
         f = self._encode_g if self.use_graph else self._encode_eager
         return f(image_primary.contiguous(), image_wrist.contiguous(), state.contiguous(), self.text_embedding(text_token))[0]
 
-    def _push(self, new_tok):
+    def _push(self, new_tok, new_frames=None):
         """queue semantics of ModelWrapper.step: append; while an episode has seen k < S frames its window is
-        [f1 .. fk, fk, ..., fk] (eval_utils_calvin.py:118-126); afterwards the window slides."""
+        [f1 .. fk, fk, ..., fk] (eval_utils_calvin.py:118-126); afterwards the window slides.  `new_frames` (B, 2, 3, h, w), with an
+        image dream only: the camera frames the tokens came from, kept for the render (the newest, or the same window with "all")."""
         B, S = self.B, self.S
+        keep_window = new_frames is not None and self.dreams_all       # sample="all": the image dream of every position needs its frame
+        if new_frames is not None and not keep_window:
+            self.frames = new_frames
         if self.tokens is None:
             self.tokens = new_tok.unsqueeze(1).expand(B, S, *new_tok.shape[1:]).contiguous()
+            if keep_window:
+                self.frames = new_frames.unsqueeze(1).expand(B, S, *new_frames.shape[1:]).contiguous()
             self.count.fill_(1)
             return
         k = self.count                                    # frames seen BEFORE this one
         full = (k >= S)
         if bool(full.all()):
             self.tokens = torch.cat((self.tokens[:, 1:], new_tok.unsqueeze(1)), dim=1)
+            if keep_window:
+                self.frames = torch.cat((self.frames[:, 1:], new_frames.unsqueeze(1)), dim=1)
         else:
             idx = torch.arange(S).unsqueeze(0).expand(B, S)
             kk = k.unsqueeze(1)
@@ -180,10 +203,13 @@ class RolloutEngine:
             ext = torch.cat((self.tokens, new_tok.unsqueeze(1)), dim=1)                  # slot S = the new frame
             gather = src.to(self.device).view(B, S, 1, 1).expand(B, S, *new_tok.shape[1:])
             self.tokens = torch.gather(ext, 1, gather)
+            if keep_window:
+                ext = torch.cat((self.frames, new_frames.unsqueeze(1)), dim=1)
+                self.frames = ext[torch.arange(B, device=self.device).view(B, 1), src.to(self.device)]
         self.count = torch.clamp(k + 1, max=S)
 
     # ------------------------------------------------------------------------------------------------------------
-    def _decode_eager(self, tokens, noise, sel):
+    def _decode_eager(self, tokens, noise, sel, frames=None):
         am = getattr(self.model, "action_model", None)
         shared = getattr(am, "team_sampler", True) if am is not None else True
         before = getattr(am, "team_launches", 0) if am is not None else 0
@@ -191,8 +217,14 @@ class RolloutEngine:
             am.team_sampler = bool(shared) and self._team_allowed      # this engine's choice for the duration of ITS decode only
         try:
             with ops.forward_split_k():       # the trunk at one episode: 930 rows, K = 4096 in the MLP down-projection
-                out = self.model.decode_tokens(tokens, mode="test", test_noise=noise if self.needs_noise else None,
-                                               test_select=None if self.sample_all else sel)
+                if not self.dreams:
+                    out = self.model.decode_tokens(tokens, mode="test", test_noise=noise if self.needs_noise else None,
+                                                   test_select=None if self.sample_all else sel)
+                else:
+                    # (the MLP action head ignores test_select: with it the dream heads run on the executed position only)
+                    out = self.model.decode_tokens(tokens, mode="test", test_noise=noise if self.needs_noise else None,
+                                                   test_select=None if (self.sample_all and self.dreams_all) else sel,
+                                                   dreams=self.dreams)
         finally:
             if am is not None:
                 am.team_sampler = shared
@@ -200,11 +232,36 @@ class RolloutEngine:
                 self._team_in_decode = getattr(am, "team_launches", 0) > before
                 if self._team_in_decode:          # the workspace of the launch just made (DDIM or flow matching, any step count)
                     self._team_entry = getattr(am, "team_entry", None)
-        return out[0], out[1]
+        return (out[0], out[1], *self._render(out, frames))
+
+    _DREAM_SLOT = {"image": 2, "depth": 6, "traj": 7, "dino": 8, "sam": 9}       # positions in decode_tokens' 10-tuple
+
+    def _render(self, out, frames):
+        """the requested heads' predictions of one decode -> what `last_dreams` holds, in the order of `self.dreams`: image uint8
+        (B, [S,] views, h, w, 3) rendered against the kept frames, depth float32 (B, [S,] views, h, w), features as they are
+        (B, [S,] views, rows, cols); a pred_num axis follows `views` when the model predicts more than one frame"""
+        res = []
+        lead = (self.B, self.S) if self.dreams_all else (self.B,)
+        for name in self.dreams:
+            p = out[self._DREAM_SLOT[name]]                       # (B [* S], views, pred_num, rows, cols)
+            views, pn = p.shape[1], p.shape[2]
+            mid = (views,) if pn == 1 else (views, pn)
+            if name in ("image", "depth"):
+                cur = None
+                if name == "image":
+                    cur = frames.reshape(-1, *frames.shape[-3:])
+                    if pn > 1:
+                        cur = cur.unsqueeze(1).expand(-1, pn, -1, -1, -1).reshape(-1, *frames.shape[-3:])
+                r = ops.dream_render(p.reshape(-1, *p.shape[3:]), name, cur, patch=self.model.PATCH_SIZE)
+                res.append(r.view(*lead, *mid, *r.shape[1:]))
+            else:
+                res.append(p.reshape(*lead, *mid, *p.shape[3:]))
+        return res
 
     @torch.no_grad()
     def _decode(self, tokens, noise, sel):
-        return (self._decode_g if self.use_graph else self._decode_eager)(tokens, noise, sel)
+        args = (tokens, noise, sel) + ((self.frames,) if "image" in self.dreams else ())
+        return (self._decode_g if self.use_graph else self._decode_eager)(*args)
 
     def draw_noise(self, generator=None):
         """start noise of the action sampler for one control step, float32 on the device: (B*S, action_pred_steps, 7) -- what
@@ -226,7 +283,8 @@ class RolloutEngine:
         gripper (B,S,steps,1); with the DiT head and sample="newest" the last two are (B,1,steps,.): the executed position
         only).  `noise`: the DiT sampler's start noise (see draw_noise; a (B*S, steps, 7) draw is accepted with "newest" too --
         the executed position's rows are taken); None = drawn here.
-        `text_token`: see `text=` of the constructor -- by default an episode keeps the instruction of its first step after a reset."""
+        `text_token`: see `text=` of the constructor -- by default an episode keeps the instruction of its first step after a reset.
+        With `dreams=` the dreams of this step are in `self.last_dreams` afterwards (clones: valid until the caller drops them)."""
         if self.text_mode == "latched":
             fresh = (self.count == 0) if self.tokens is not None else torch.ones(self.B, dtype=torch.bool)
             if self._latched is None or bool(fresh.all()):
@@ -244,9 +302,9 @@ class RolloutEngine:
 
     def _step(self, image_primary, image_wrist, state, text_token, noise):
         dt = self.dtype
-        new_tok = self.encode_newest(image_primary.to(self.device, dt), image_wrist.to(self.device, dt),
-                                     state.to(self.device, dt), text_token.to(self.device))
-        self._push(new_tok)
+        image_primary, image_wrist = image_primary.to(self.device, dt), image_wrist.to(self.device, dt)
+        new_tok = self.encode_newest(image_primary, image_wrist, state.to(self.device, dt), text_token.to(self.device))
+        self._push(new_tok, torch.stack((image_primary, image_wrist), dim=1) if "image" in self.dreams else None)
         # the wrapper conditions EVERY frame of the window on the current instruction (eval_utils_calvin.py:127-134 repeat the
         # text over the window), so the text token (slot 0 of a frame's 36) is not history: all S frames carry today's embedding
         self.tokens[:, :, 0] = self._text_emb.to(self.tokens.dtype).unsqueeze(1)
@@ -264,7 +322,8 @@ class RolloutEngine:
             noise = noise.to(self.device, torch.float32)
             if not self.sample_all and noise.shape[0] == B * S and S > 1:
                 noise = noise.view(B, S, *noise.shape[1:])[bi, sel]
-        action, arm, grip = self._actions(*self._decode(self.tokens, noise, sel), sel, bi)
+        out = self._decode(self.tokens, noise, sel)
+        action, arm, grip = self._actions(out[0], out[1], sel, bi)
         if self._team_sampler_in_use() and self._team_timed_out():
             # The one-XCD sampler kernel (dvla_dit_sample) bounds every wait; on a GPU that other work keeps busy its 32 workgroups
             # may not be co-resident, a wait times out and the kernel returns NaN by design.  Under hipGraph replay no Python runs
@@ -275,7 +334,10 @@ class RolloutEngine:
             # timeout and must not switch the sampler).  Recovery: the launch-by-launch sampler (same arithmetic) for THIS engine,
             # its decode graph re-captured, this step's action recomputed from the same tokens and noise.
             self._team_fallback()
-            action, arm, grip = self._actions(*self._decode(self.tokens, noise, sel), sel, bi)
+            out = self._decode(self.tokens, noise, sel)
+            action, arm, grip = self._actions(out[0], out[1], sel, bi)
+        # the dreams of the decode whose action is returned (after a fallback: of the recomputed one)
+        self.last_dreams = dict(zip(self.dreams, out[2:]))
         return action, arm, grip
 
     def _actions(self, arm, grip, sel, bi):

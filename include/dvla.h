@@ -419,6 +419,28 @@ int dvla_image_preprocess(const uint8_t* src, const int32_t* shift, void* out, i
                           int32_t pad, const float* mean3, const float* std3, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Dreams at evaluation (an addition: the reference decodes its image / depth / feature predictions in mode="train" only).
+ * dvla_gather_positions: out[b, t, :] = x[b, sel[b], tok_begin + t, :] -- the query rows of ONE window position per sequence
+ *   (the position the evaluation wrapper executes) out of the trunk output x (B, S, T, H), read in place.  bf16, contiguous,
+ *   16-byte aligned, H % 8 == 0; sel (B,) int64 on the device, clamped to [0, S).  out (B, tok_count, H).
+ * dvla_dream_render: patch predictions -> frames, one launch, nothing but the frame written.  pred (n, grid_h * grid_w,
+ *   patch * patch * channels) bf16 in the reference's patch layout (utils/train_utils.py:37-50 'nchpwq->nhwpqc': the values of
+ *   a patch in (p, q, c) order).
+ *   current == NULL: un-patchify only (utils/train_utils.py:783-799) -> out (n, channels, patch grid_h, patch grid_w) fp32;
+ *     channels 3 (the image head, in the normalised space it was trained in) or 1 (the depth head).
+ *   current != NULL (channels == 3): the model's own input frame (n, 3, patch grid_h, patch grid_w) bf16, CLIP-normalised.  The
+ *     head's target is normalize_patchfied_image of the future frame (utils/train_utils.py:52-57); it is inverted with the mean
+ *     and the unbiased variance of the SAME patch of `current` (x = pred * sqrt(var + 1e-6) + mean), then CLIP's Normalize is
+ *     inverted with mean3 / std3 (x * std + mean), clamped to [0, 1], scaled by 255, rounded half-to-even
+ *     -> out (n, patch grid_h, patch grid_w, 3) uint8.  fp32 arithmetic.
+ *   patch == 16 (one wave per patch); anything else, or a misaligned base (pred / current 8, out 16 bytes):
+ *   DVLA_ERR_UNSUPPORTED. */
+int dvla_gather_positions(const void* x, const int64_t* sel, void* out, int32_t B, int32_t S, int32_t T, int32_t H,
+                          int32_t tok_begin, int32_t tok_count, void* stream);
+int dvla_dream_render(const void* pred, const void* current, void* out, int64_t n, int32_t grid_h, int32_t grid_w, int32_t patch,
+                      int32_t channels, const float* mean3, const float* std3, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * MAE pretraining (models/vit_mae.py:129-256): random masking, the decoder's token un-shuffle and the patch-MSE loss, each
  * one pass instead of the reference's argsort / gather / cat / add / patchify / mean / var chains.  Deterministic: no float
  * atomics, fixed-order two-stage sums.  bf16 activations, fp32 arithmetic; all tensors contiguous unless a stride is given,
