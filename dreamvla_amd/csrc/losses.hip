@@ -233,6 +233,11 @@ inline View view_of(const dvla_frame_view& v) {
 inline ViewW viewW_of(const dvla_frame_view& v) {
   return ViewW{reinterpret_cast<bf16_t*>(const_cast<void*>(v.base)), v.stride_b, v.stride_t, v.T > 0 ? v.T : 1};
 }
+// the cosine kernels read and write rows as 16-byte vectors: every frame base must be 16-byte aligned, i.e. the view's base is
+// and both strides are multiples of 8 elements (rows inside a frame follow from cols % 8 == 0)
+inline bool vec16_ok(const dvla_frame_view& v) {
+  return (reinterpret_cast<uintptr_t>(v.base) & 15) == 0 && v.stride_b % 8 == 0 && v.stride_t % 8 == 0;
+}
 
 }  // namespace
 
@@ -266,7 +271,8 @@ extern "C" int dvla_cosine_loss_fwd(const dvla_frame_view* pred, const dvla_fram
                                     int64_t n_frames, float* out2, float* partial, void* stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (!pred || !label || !pred->base || !label->base || !out2 || !partial || n_frames <= 0 || rows_per_frame <= 0) return DVLA_ERR_ARG;
-  if (cols <= 0 || cols % 8 != 0 || cols > 1024) return DVLA_ERR_UNSUPPORTED;   // 16-byte vectors; frame bases must be 16-B aligned
+  if (cols <= 0 || cols % 8 != 0 || cols > 1024) return DVLA_ERR_UNSUPPORTED;
+  if (!vec16_ok(*pred) || !vec16_ok(*label)) return DVLA_ERR_UNSUPPORTED;
   const int nb = blocks_for(n_frames * rows_per_frame);
   hipLaunchKernelGGL(cosine_kernel<false>, dim3(nb), dim3(LOSS_THREADS), 0, stream, view_of(*pred), view_of(*label), rows_per_frame, cols,
                      n_frames, partial, ViewW{nullptr, 0, 0, 1}, nullptr, 0.f);
@@ -282,7 +288,8 @@ extern "C" int dvla_cosine_loss_bwd(const dvla_frame_view* pred, const dvla_fram
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (!pred || !label || !dpred || !pred->base || !label->base || !dpred->base || !grad_out || n_frames <= 0 || rows_per_frame <= 0)
     return DVLA_ERR_ARG;
-  if (cols <= 0 || cols % 8 != 0 || cols > 1024) return DVLA_ERR_UNSUPPORTED;   // 16-byte vectors; frame bases must be 16-B aligned
+  if (cols <= 0 || cols % 8 != 0 || cols > 1024) return DVLA_ERR_UNSUPPORTED;
+  if (!vec16_ok(*pred) || !vec16_ok(*label) || !vec16_ok(*dpred)) return DVLA_ERR_UNSUPPORTED;
   const int nb = blocks_for(n_frames * rows_per_frame);
   hipLaunchKernelGGL(cosine_kernel<true>, dim3(nb), dim3(LOSS_THREADS), 0, stream, view_of(*pred), view_of(*label), rows_per_frame, cols,
                      n_frames, nullptr, viewW_of(*dpred), grad_out, (float)(1.0 / ((double)n_frames * rows_per_frame)));

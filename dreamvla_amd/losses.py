@@ -32,6 +32,12 @@ def _frame_view(t):
     return FrameView(t.data_ptr(), t.stride(0), t.stride(1), t.shape[1])
 
 
+def _vec16_ok(t):
+    """the cosine kernels read rows as 16-byte vectors: a (bs, T, rows, cols) view must start 16-byte aligned and step by
+    multiples of 8 elements over batch and time (dvla_cosine_loss_* return DVLA_ERR_UNSUPPORTED otherwise)"""
+    return t.data_ptr() % 16 == 0 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0
+
+
 def _fused_ok(pred, *labels):
     return (pred is not None and pred.is_cuda and pred.dtype == torch.bfloat16
             and all(lb.is_cuda and lb.dtype == torch.bfloat16 for lb in labels))
@@ -213,7 +219,10 @@ def calvin_losses(outputs, batch, *, sequence_length, future_steps=3, atten_goal
         parts["depth"] = 0.5 * (silog_loss(dx, dlab("depth_primary")) + silog_loss(dg, dlab("depth_wrist")))
 
     def cos_loss(pred, key_p, key_w):
-        if use_fused(pred, key_p, key_w) and pred.shape[-1] % 64 == 0 and pred.shape[-1] <= 1024:
+        aligned = all(_vec16_ok(batch[k][:, lo:hi]) for k in (key_p, key_w)) and (not pred.is_contiguous() or pred.data_ptr() % 16 == 0)
+        if fused is True and not aligned:
+            raise TypeError("fused cosine loss needs 16-byte aligned predictions / labels")
+        if use_fused(pred, key_p, key_w) and pred.shape[-1] % 64 == 0 and pred.shape[-1] <= 1024 and aligned:
             return two_view_loss("cosine", pred, batch[key_p][:, lo:hi], batch[key_w][:, lo:hi], bs, S, T)
         pp = pred.reshape(bs, S, *pred.shape[1:])[:, :T].reshape(-1, *pred.shape[1:]).to(compute_dtype)
         lp = batch[key_p][:, lo:hi].reshape(-1, *batch[key_p].shape[2:]).to(compute_dtype)

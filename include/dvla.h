@@ -378,7 +378,8 @@ int dvla_patch_mse_fwd(const dvla_frame_view* pred, const dvla_frame_view* image
                        float* out2, float* partial, void* stream);
 int dvla_patch_mse_bwd(const dvla_frame_view* pred, const dvla_frame_view* image, const float* patch_mask, int64_t n_frames,
                        const float* grad_out, const dvla_frame_view* dpred, void* stream);
-/* pred / label frames (rows_per_frame, cols); cols % 64 == 0, cols <= 1024 */
+/* pred / label frames (rows_per_frame, cols); cols % 8 == 0, cols <= 1024, and every view 16-byte aligned (base, and both
+ * strides multiples of 8 elements): rows are read as 16-byte vectors.  DVLA_ERR_UNSUPPORTED otherwise, before any launch. */
 int dvla_cosine_loss_fwd(const dvla_frame_view* pred, const dvla_frame_view* label, int32_t rows_per_frame, int32_t cols,
                          int64_t n_frames, float* out2, float* partial, void* stream);
 int dvla_cosine_loss_bwd(const dvla_frame_view* pred, const dvla_frame_view* label, int32_t rows_per_frame, int32_t cols,
