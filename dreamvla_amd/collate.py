@@ -4,10 +4,12 @@
 The reference collator runs the CLIP image transform on every PIL frame on the host (`self.image_fn` = `preprocess_image`,
 data_utils.py:175-179: Resize / CenterCrop / ToTensor / Normalize -> fp32 (3, 224, 224) = 602 KB per frame), stacks, applies
 `RandomShiftsAug` with `grid_sample` on the host (1336-1355), and the training loop then uploads fp32 and casts
-(utils/train_utils.py:99-100).  Here the host does only what needs PIL (the antialiased bicubic resize + crop, to uint8 HWC =
+(utils/train_utils.py:99-100).  Here, by default, the host does only what needs PIL (the antialiased bicubic resize + crop, to uint8 HWC =
 150 KB per frame); the resized frames go to the device in ONE pinned, asynchronous copy per camera and
 `dreamvla_amd.preprocess.preprocess_frames` (csrc/input_pipeline.hip) does ToTensor + Normalize + the shift gather + the bf16
-cast in one kernel.  The instruction strings are tokenised through a per-string cache (CALVIN has 34 tasks x a few phrasings;
+cast in one kernel.  With `device_resize=True` the host does not resize either: the raw frames (120 KB / 21 KB per CALVIN frame)
+are uploaded and `preprocess.resize_frames_u8` (csrc/image_resize.hip) produces the same uint8 frames, byte for byte, on the device.
+The instruction strings are tokenised through a per-string cache (CALVIN has 34 tasks x a few phrasings;
 the reference re-tokenises every sample of every batch, data_utils.py:181-183).  Everything else of the collator -- states,
 actions, the `act_step` chunking, depth / DINO / SAM / track labels -- is host tensor bookkeeping and is kept as it is.
 
@@ -62,7 +64,7 @@ class DeviceCollator:
     `load_track_labels`), and every sample must carry an `episode_id` (:2726)."""
 
     def __init__(self, tokenize, window_size, rgb_pad=-1, gripper_pad=-1, traj_cons=False, act_step=1, n_px=224,
-                 device="cuda", load_track_labels=False, generator=None, dataset="calvin"):
+                 device="cuda", load_track_labels=False, generator=None, dataset="calvin", device_resize=False):
         if dataset not in ("calvin", "libero"):
             raise ValueError(f"dataset {dataset!r}: 'calvin' or 'libero'")
         self.dataset = dataset
@@ -71,11 +73,29 @@ class DeviceCollator:
         self.rgb_pad, self.gripper_pad, self.traj_cons = rgb_pad, gripper_pad, traj_cons
         self.n_px, self.device, self.load_track_labels = n_px, torch.device(device), load_track_labels
         self.generator = generator
+        # device_resize: the raw frames of a camera (one size per camera) cross PCIe as they are and CLIP's bicubic Resize +
+        # CenterCrop runs on the device too (preprocess.resize_frames_u8: bit-identical to the Pillow resize of the default path)
+        self.device_resize = bool(device_resize)
 
     # ---- camera frames: PIL -> uint8 HWC on the host, everything else on the device -------------------------------------
     def _frames_u8(self, sample, cam):
         arr = np.stack([np.stack([P.clip_image_resize_u8(f, self.n_px) for f in s["rgb_obs"][cam]]) for s in sample])
         t = torch.from_numpy(arr)                               # (B, T, H, W, 3) uint8
+        if self.device.type == "cuda":
+            t = t.pin_memory()
+        return t
+
+    def _raw_frames_u8(self, sample, cam):
+        """the camera's frames as they come from the dataset, stacked: (B, T, h, w, 3) uint8"""
+        rows = [[np.asarray(P._to_pil(f), dtype=np.uint8) for f in s["rgb_obs"][cam]] for s in sample]
+        if any(a.ndim != 3 or a.shape[2] != 3 for row in rows for a in row):
+            # (the host path resizes in the image's own mode and converts to RGB afterwards: not the same bytes for other modes)
+            raise ValueError(f"DeviceCollator(device_resize=True): the {cam} frames must be RGB (h, w, 3) images")
+        sizes = sorted({a.shape[:2] for row in rows for a in row})
+        if len(sizes) != 1:
+            raise ValueError(f"DeviceCollator(device_resize=True): the {cam} frames of a batch must have one size, got (h, w) = "
+                             f"{sizes}; resize on the host (device_resize=False) or batch by camera resolution")
+        t = torch.from_numpy(np.stack([np.stack(row) for row in rows]))
         if self.device.type == "cuda":
             t = t.pin_memory()
         return t
@@ -89,10 +109,12 @@ class DeviceCollator:
         return P.draw_shifts(n, pad, traj=self.traj_cons, generator=self.generator)
 
     def _camera(self, sample, cam, pad):
-        u8 = self._frames_u8(sample, cam)
+        u8 = self._raw_frames_u8(sample, cam) if self.device_resize else self._frames_u8(sample, cam)
         B, T = u8.shape[:2]
         shifts = None if pad == -1 else self._shifts(B * T, pad, cam)
         dev = u8.to(self.device, non_blocking=True)
+        if self.device_resize:
+            dev = P.resize_frames_u8(dev, self.n_px)
         return P.preprocess_frames(dev, shifts, 0 if pad == -1 else pad)             # (B, T, 3, H, W) bf16, one kernel
 
     def _depth(self, sample, cam, pad):

@@ -112,6 +112,7 @@ class RolloutEngine:
         self.dreams = DreamVLA._check_dreams(m, dreams)
         self.dreams_all = (sample == "all")
         self.last_dreams = {}
+        self.last_frames_u8 = None              # step_raw: the resized camera frames of the last step, (B, 2, n_px, n_px, 3) uint8
         self.frames = None                      # newest real frame (B, 2, 3, h, w), or the window's (B, S, 2, 3, h, w) with "all"
         # Instruction text.  "latched" = the wrapper's semantics, literally (eval_utils_calvin.py:109-112: `text_queue` is filled
         # once, when it is empty -- i.e. at the first step after `reset()` -- and kept): an episode's instruction is the one it was
@@ -299,6 +300,31 @@ class RolloutEngine:
             # already pushed: fall back and decode this step again
             self._team_fallback()
             return self._finish_step(noise)
+
+    def _raw_to_device(self, frames_u8):
+        if not isinstance(frames_u8, torch.Tensor):
+            import numpy as np
+            frames_u8 = torch.from_numpy(np.ascontiguousarray(frames_u8))
+        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[0] != self.B or frames_u8.shape[-1] != 3:
+            raise TypeError(f"step_raw: uint8 camera frames ({self.B}, h, w, 3) expected")
+        if not frames_u8.is_cuda and self.device.type == "cuda":
+            frames_u8 = frames_u8.pin_memory()                    # one asynchronous copy per camera, as the collator's
+        return frames_u8.to(self.device, non_blocking=True)
+
+    @torch.no_grad()
+    def step_raw(self, frames_primary_u8, frames_wrist_u8, state, text_token, noise=None, n_px=224):
+        """`step` from the simulator's raw camera frames: (B, h, w, 3) uint8 per camera, host (numpy array or tensor) or device,
+        one size per camera.  Upload, CLIP's bicubic Resize + CenterCrop on the device (preprocess.resize_frames_u8: the bytes
+        Pillow produces), ToTensor + Normalize + cast (preprocess.preprocess_frames), then `step`: same return value, and the
+        same actions bit for bit as `step` on host-resized frames.  The resized frames of this step stay in
+        `self.last_frames_u8` (B, 2, n_px, n_px, 3) uint8 on the device, view 0 = primary, 1 = wrist (the layout of
+        `last_dreams["image"]`)."""
+        from . import preprocess as P
+        u8 = torch.stack((P.resize_frames_u8(self._raw_to_device(frames_primary_u8), n_px),
+                          P.resize_frames_u8(self._raw_to_device(frames_wrist_u8), n_px)), dim=1)
+        x = P.preprocess_frames(u8)                               # (B, 2, 3, n_px, n_px) bf16
+        self.last_frames_u8 = u8
+        return self.step(x[:, 0], x[:, 1], state, text_token, noise)
 
     def _step(self, image_primary, image_wrist, state, text_token, noise):
         dt = self.dtype

@@ -418,6 +418,23 @@ int dvla_mask_tables(const dvla_mask_rule* rule, const int32_t* drop, int32_t* k
  * augmentation); out: (n, 3, H, W) bf16, 16-byte aligned; W % 8 == 0. */
 int dvla_image_preprocess(const uint8_t* src, const int32_t* shift, void* out, int64_t n, int32_t height, int32_t width,
                           int32_t pad, const float* mean3, const float* std3, void* stream);
+/* (additive, ABI 8) The head of that transform, Resize(n_px, BICUBIC) + CenterCrop(n_px), on raw uint8 frames, byte for byte what
+ * Pillow's 8-bit resample gives: integer arithmetic on tables the CALLER builds in float64 exactly as Pillow does
+ * (dreamvla_amd/preprocess.py: bicubic_tables).  src: (n, src_h, src_w, 3) uint8, contiguous, any alignment.
+ * The frame is resampled to res_h x res_w -- horizontally first, that result rounded to uint8, then vertically -- of which
+ * out (n, n_px, n_px, 3) uint8 is the window at (crop_top, crop_left); only that window is computed.  Per axis: bounds (res, 2)
+ * int32 = (first input index, tap count <= ksize) of every output index, 8-byte aligned; coef (res, ksize) int32 = the taps'
+ * coefficients at 22 fractional bits;  output byte = clamp((2^21 + sum_t in[first + t] * coef[t]) >> 22, 0, 255)  in a signed 32-bit
+ * accumulator.  An axis whose input and output size are equal is NOT resampled by Pillow: pass the identity table for it (bounds
+ * (i, 1), coef 2^22, ksize 1).  One launch; the intermediate rows stay in LDS.
+ * DVLA_ERR_ARG: a null pointer, a size < 1, a crop window outside res_h x res_w.  DVLA_ERR_UNSUPPORTED: the LDS plan of ONE
+ * output row -- ksize_y rows of align16(3 n_px) bytes plus four staging buffers of 3 (min(src_w, ceil((n_px - 1) src_w / res_w) +
+ * ksize_x)) + 31 bytes -- exceeds 64 KiB (at n_px = 224: sources up to 10 x n_px on their shorter side all fit, whatever the
+ * longer side; 84 x 84, 200 x 200, 480 x 640 and 720 x 1280 run at 16 output rows per workgroup), src_h or src_w > 2^20,
+ * n_px > 2^14, or more than 2^31 - 1 workgroups (n x ceil(n_px / rows per workgroup)). */
+int dvla_image_resize_u8(const uint8_t* src, uint8_t* out, int64_t n, int32_t src_h, int32_t src_w, int32_t res_h, int32_t res_w,
+                         const int32_t* bounds_x, const int32_t* coef_x, int32_t ksize_x, const int32_t* bounds_y,
+                         const int32_t* coef_y, int32_t ksize_y, int32_t crop_left, int32_t crop_top, int32_t n_px, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Dreams at evaluation (an addition: the reference decodes its image / depth / feature predictions in mode="train" only).
