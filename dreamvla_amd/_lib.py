@@ -139,6 +139,7 @@ SYMBOLS = {
     "dvla_mask_tables": (C.c_int, [C.POINTER(MaskRule), _P, _P, _P, _P, _P, _P]),
     "dvla_image_preprocess": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float), _P]),
     "dvla_image_resize_u8": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _I32, _I32, _I32, _I32, _P]),
+    "dvla_depth_preprocess": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "dvla_gather_positions": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "dvla_dream_render": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float), _P]),
     "dvla_loss_partial_len": (C.c_int64, []),

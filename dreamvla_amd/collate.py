@@ -11,7 +11,11 @@ cast in one kernel.  With `device_resize=True` the host does not resize either: 
 are uploaded and `preprocess.resize_frames_u8` (csrc/image_resize.hip) produces the same uint8 frames, byte for byte, on the device.
 The instruction strings are tokenised through a per-string cache (CALVIN has 34 tasks x a few phrasings;
 the reference re-tokenises every sample of every batch, data_utils.py:181-183).  Everything else of the collator -- states,
-actions, the `act_step` chunking, depth / DINO / SAM / track labels -- is host tensor bookkeeping and is kept as it is.
+actions, the `act_step` chunking, depth / DINO / SAM / track labels -- is host tensor bookkeeping and is kept as it is by default.
+With `device_labels=True` the labels take the cameras' route: the raw depth maps of a camera are stacked into pinned memory, uploaded
+in one asynchronous copy and resized / shifted / cast by `preprocess.preprocess_depth` (csrc/depth_pipeline.hip); the DINO / SAM
+features and the track dictionary are stacked into pinned memory, uploaded, and the features cast on the device.  Every label entry
+then equals the default's `.to(device, label_dtype)` bit for bit (the tracks keep their dtype), DESIGN.md section 4.3.2.
 
 The returned tuple has the reference's layout (13 entries); entries 0 and 3 (static / gripper camera) are bf16 CUDA tensors
 (B, T, 3, 224, 224), so the loop's `.to(device_id, dtype=cast_dtype, non_blocking=True)` on them is a no-op."""
@@ -64,7 +68,8 @@ class DeviceCollator:
     `load_track_labels`), and every sample must carry an `episode_id` (:2726)."""
 
     def __init__(self, tokenize, window_size, rgb_pad=-1, gripper_pad=-1, traj_cons=False, act_step=1, n_px=224,
-                 device="cuda", load_track_labels=False, generator=None, dataset="calvin", device_resize=False):
+                 device="cuda", load_track_labels=False, generator=None, dataset="calvin", device_resize=False,
+                 device_labels=False, label_dtype=torch.bfloat16):
         if dataset not in ("calvin", "libero"):
             raise ValueError(f"dataset {dataset!r}: 'calvin' or 'libero'")
         self.dataset = dataset
@@ -76,6 +81,13 @@ class DeviceCollator:
         # device_resize: the raw frames of a camera (one size per camera) cross PCIe as they are and CLIP's bicubic Resize +
         # CenterCrop runs on the device too (preprocess.resize_frames_u8: bit-identical to the Pillow resize of the default path)
         self.device_resize = bool(device_resize)
+        # device_labels: entries 6 .. 11 (depth, DINO, SAM) leave the collator on the device in label_dtype, the track dictionary on
+        # the device in its own dtypes -- the loss kernels take them as they are (losses.calvin_losses)
+        self.device_labels, self.label_dtype = bool(device_labels), label_dtype
+        if self.device_labels and label_dtype not in (torch.bfloat16, torch.float32):
+            raise ValueError(f"DeviceCollator(device_labels=True): label_dtype {label_dtype}: torch.bfloat16 or torch.float32")
+        if self.device_labels and self.device.type != "cuda":
+            raise ValueError(f"DeviceCollator(device_labels=True): device {self.device}: the label path has no CPU fallback")
 
     # ---- camera frames: PIL -> uint8 HWC on the host, everything else on the device -------------------------------------
     def _frames_u8(self, sample, cam):
@@ -125,29 +137,68 @@ class DeviceCollator:
             d = P.shift_gather_reference(d.view(B * T, *d.shape[2:]), sh, pad).view_as(d)
         return d
 
+    # ---- device_labels=True: the labels stacked into pinned memory, one asynchronous copy per entry -----------------------
+    # Staging: a FRESH pinned buffer per entry and call (torch.empty(pin_memory=True)), never one the collator keeps and rewrites.
+    # torch's pinned-memory allocator hands a freed block out again only after the copies enqueued from it have completed (it
+    # records an event per non_blocking copy), so the next call cannot overwrite a buffer an in-flight copy still reads, and
+    # after the first batches the blocks come out of its cache.
+    def _upload_stacked(self, tensors):
+        """torch.stack(tensors) written straight into pinned memory -> the same tensor on the device (copy enqueued, not waited for)"""
+        buf = torch.empty((len(tensors), *tensors[0].shape), dtype=tensors[0].dtype, pin_memory=True)
+        torch.stack(tensors, out=buf)
+        return buf.to(self.device, non_blocking=True)
+
+    def _feature_labels(self, tensors):
+        from . import ops
+        return ops.cast_to(self._upload_stacked(tensors), self.label_dtype)    # fp32 <-> bf16 on the device; anything else raises
+
+    def _depth_device(self, sample, cam, pad):
+        """`_depth` with the raw maps on the device: (B, T, h, w) fp32 pinned -> one copy -> preprocess_depth"""
+        rows = [[np.asarray(img, dtype=np.float32) for img in s["depth_obs"][cam]] for s in sample]
+        if any(a.ndim != 2 for row in rows for a in row):
+            raise ValueError("Depth images should have shape (N, H, W)")
+        sizes = sorted({a.shape for row in rows for a in row})
+        if len({len(row) for row in rows}) != 1:
+            raise ValueError(f"DeviceCollator(device_labels=True): the samples of a batch must hold the same number of {cam} frames")
+        if len(sizes) != 1:
+            raise ValueError(f"DeviceCollator(device_labels=True): the {cam} frames of a batch must have one size, got (h, w) = "
+                             f"{sizes}; resize on the host (device_labels=False) or batch by camera resolution")
+        B, T = len(rows), len(rows[0])
+        buf = torch.empty((B, T, *sizes[0]), dtype=torch.float32, pin_memory=True)
+        stage = buf.numpy()
+        for b, row in enumerate(rows):
+            for t, a in enumerate(row):
+                stage[b, t] = a
+        shifts = self._shifts(B * T, pad, cam) if (pad != -1 and self.traj_cons) else None     # the conditions and the order of `_depth`
+        dev = buf.to(self.device, non_blocking=True)
+        return P.preprocess_depth(dev, shifts, 0 if shifts is None else pad, self.n_px, self.label_dtype)   # (B, T, 1, H, W), one kernel
+
     def __call__(self, sample):
         action_tensors = torch.from_numpy(np.array([np.stack(s["actions"]) for s in sample]))
         state_tensors = torch.from_numpy(np.array([np.stack(s["robot_obs"]) for s in sample]))
         libero = self.dataset == "libero"
         has_depth = (not libero) and "depth_obs" in sample[0]
         image_tensors = self._camera(sample, "rgb_static", self.rgb_pad)
-        depth_static = self._depth(sample, "depth_static", self.rgb_pad) if has_depth else None
+        depth_fn = self._depth_device if self.device_labels else self._depth
+        stack = self._upload_stacked if self.device_labels else torch.stack
+        features = self._feature_labels if self.device_labels else torch.stack
+        depth_static = depth_fn(sample, "depth_static", self.rgb_pad) if has_depth else None
         gripper_tensors = self._camera(sample, "rgb_gripper", self.gripper_pad)
-        depth_gripper = self._depth(sample, "depth_gripper", self.gripper_pad) if has_depth else None
+        depth_gripper = depth_fn(sample, "depth_gripper", self.gripper_pad) if has_depth else None
         if libero:
             _ = [s["episode_id"] for s in sample]        # KeyError on a sample without one, like the reference
         text_tensors = self.text_fn([s["lang"] for s in sample])
         tracks = {}
         if "track_label" in sample[0]:
-            tracks = {k: torch.stack([s["track_label"][k] for s in sample])
+            tracks = {k: stack([s["track_label"][k] for s in sample])
                       for k in ("tracks", "track_visibility", "tracks_gripper", "track_visibility_gripper")}
         dino = dino_g = sam = sam_g = None
         if "dino_features_obs" in sample[0]:
-            dino = torch.stack([s["dino_features_obs"]["dino_feats_static"] for s in sample])
-            dino_g = torch.stack([s["dino_features_obs"]["dino_feats_gripper"] for s in sample])
+            dino = features([s["dino_features_obs"]["dino_feats_static"] for s in sample])
+            dino_g = features([s["dino_features_obs"]["dino_feats_gripper"] for s in sample])
         if "sam_features_obs" in sample[0]:
-            sam = torch.stack([s["sam_features_obs"]["sam_feats_static"] for s in sample])
-            sam_g = torch.stack([s["sam_features_obs"]["sam_feats_gripper"] for s in sample])
+            sam = features([s["sam_features_obs"]["sam_feats_static"] for s in sample])
+            sam_g = features([s["sam_features_obs"]["sam_feats_gripper"] for s in sample])
         robot_obs = torch.zeros(1)
         if self.act_step != 1:                      # data_utils.py:1359-1391
             a = self.act_step

@@ -11,7 +11,10 @@ torchvision's Resize / CenterCrop on a PIL image are `Image.resize((w', h'), BIC
 `resize_frames_u8` is that Resize + CenterCrop on the device (csrc/image_resize.hip), byte for byte Pillow's: Pillow resamples
 8-bit images in fixed point on coefficient tables computed once per (input size, output size) in double precision, so the
 tables are built here on the host exactly as Pillow builds them (`bicubic_tables`) and the kernel does integer arithmetic only;
-`resize_u8_reference` is the same integer arithmetic in numpy, the host mirror of the kernel."""
+`resize_u8_reference` is the same integer arithmetic in numpy, the host mirror of the kernel.
+
+`preprocess_depth` is the depth labels' counterpart of `preprocess_frames` (csrc/depth_pipeline.hip): the collator's nearest resize
+of the raw fp32 depth maps, the shift gather and the cast in one kernel; `depth_resize_reference` is its host mirror."""
 import functools
 import math
 
@@ -244,3 +247,62 @@ def preprocess_frames(frames_u8, shifts=None, pad=0, mean=CLIP_MEAN, std=CLIP_ST
     _lib.check(lib.dvla_image_preprocess(src.data_ptr(), None if sh is None else sh.data_ptr(), out.data_ptr(), n, H, W, int(pad),
                                          m3, s3, _stream()), "dvla_image_preprocess")
     return out.view(*lead, 3, H, W)
+
+
+def nearest_index(insz, outsz):
+    """ATen's nearest-neighbour source index of every output index, as F.interpolate(mode="nearest") computes it on a float
+    tensor: min(int(floorf(j * (float(insz) / outsz))), insz - 1), the scale and the product in fp32.  (outsz,) int64."""
+    scale = np.float32(insz) / np.float32(outsz)
+    idx = np.floor(np.arange(outsz, dtype=np.float32) * scale).astype(np.int64)
+    return torch.from_numpy(np.minimum(idx, insz - 1))
+
+
+def depth_resize_reference(depth, shifts=None, pad=0, size=224):
+    """`collate.depth_image_fn` followed by RandomShiftsAug, as the gather the two are (exact: no arithmetic on the values):
+    depth (n, h, w) fp32 CPU tensor, shifts (n, 2) ints (sx, sy) or None -> (n, 1, size, size) fp32,
+        out[i, 0, y, x] = depth[i, ry[clamp(y + sy_i - pad, 0, size - 1)], rx[clamp(x + sx_i - pad, 0, size - 1)]]
+    with ry / rx = `nearest_index`.  Host-side mirror of dvla_depth_preprocess (csrc/depth_pipeline.hip); tests pin it against
+    F.interpolate and `shift_gather_reference` bit for bit."""
+    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or depth.dim() != 3:
+        raise TypeError("depth_resize_reference: fp32 tensor (n, h, w) expected")
+    n, h, w = depth.shape
+    ys = torch.arange(size).view(1, size).expand(n, size)
+    xs = torch.arange(size).view(1, size).expand(n, size)
+    if shifts is not None and pad > 0:
+        ys = ys + shifts[:, 1].view(n, 1).long() - pad
+        xs = xs + shifts[:, 0].view(n, 1).long() - pad
+    ys, xs = nearest_index(h, size)[ys.clamp(0, size - 1)], nearest_index(w, size)[xs.clamp(0, size - 1)]
+    return depth[torch.arange(n).view(n, 1, 1), ys.view(n, size, 1), xs.view(n, 1, size)].unsqueeze(1)
+
+
+def preprocess_depth(depth_f32, shifts=None, pad=0, size=224, dtype=torch.bfloat16):
+    """depth_f32: (..., h, w) fp32 CUDA tensor (raw depth maps of one size); shifts: (n, 2) int32 (sx, sy) or None.
+    -> (..., 1, size, size) `dtype` (bf16 or fp32) on the device: nearest resize + RandomShiftsAug + cast, one HIP kernel
+    (no CPU fallback).  A non-contiguous input is made contiguous first."""
+    from . import _lib
+    from .ops import _stream
+    if not isinstance(depth_f32, torch.Tensor) or depth_f32.dtype != torch.float32:
+        raise TypeError("preprocess_depth: fp32 tensor (..., h, w) expected")
+    if not depth_f32.is_cuda:
+        raise _lib.DvlaError(f"preprocess_depth: tensor is on {depth_f32.device}; the HIP input pipeline has no CPU fallback")
+    lib = _lib.load()
+    if dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"preprocess_depth: dtype {dtype}: torch.bfloat16 or torch.float32")
+    if depth_f32.dim() < 2:
+        raise ValueError("preprocess_depth: depth maps (..., h, w) expected")
+    lead, (h, w) = depth_f32.shape[:-2], depth_f32.shape[-2:]
+    size = int(size)
+    if h < 1 or w < 1 or size < 1:
+        raise ValueError("preprocess_depth: empty depth maps")
+    src = depth_f32.reshape(-1, h, w).contiguous()
+    n = src.shape[0]
+    sh = None
+    if shifts is not None:
+        sh = shifts.to(device=src.device, dtype=torch.int32).reshape(n, 2).contiguous()
+    out = torch.empty((n, 1, size, size), dtype=dtype, device=src.device)
+    if n == 0:
+        return out.view(*lead, 1, size, size)
+    _lib.check(lib.dvla_depth_preprocess(src.data_ptr(), None if sh is None else sh.data_ptr(), out.data_ptr(), n, h, w, size, size,
+                                         int(pad), _lib.DT_BF16 if dtype == torch.bfloat16 else _lib.DT_F32, _stream()),
+               "dvla_depth_preprocess")
+    return out.view(*lead, 1, size, size)

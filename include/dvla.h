@@ -435,6 +435,18 @@ int dvla_image_preprocess(const uint8_t* src, const int32_t* shift, void* out, i
 int dvla_image_resize_u8(const uint8_t* src, uint8_t* out, int64_t n, int32_t src_h, int32_t src_w, int32_t res_h, int32_t res_w,
                          const int32_t* bounds_x, const int32_t* coef_x, int32_t ksize_x, const int32_t* bounds_y,
                          const int32_t* coef_y, int32_t ksize_y, int32_t crop_left, int32_t crop_top, int32_t n_px, void* stream);
+/* (additive, ABI 8) Depth labels on the device: raw fp32 depth maps -> the collator's nearest resize
+ * (`depth_image_fn`, utils/data_utils.py:3588-3607 = F.interpolate(mode="nearest")) -> RandomShiftsAug as the integer-shift gather
+ * -> cast, one launch:
+ *   out[i, y, x] = cast(src[i, ry(clamp(y + sy_i - pad, 0, out_h - 1)), rx(clamp(x + sx_i - pad, 0, out_w - 1))])
+ *   ry(j) = min((int)floorf(j * ((float)src_h / out_h)), src_h - 1), rx(j) likewise with the widths (ATen's source index, fp32).
+ * src: (n, src_h, src_w) fp32, contiguous; shift: (n, 2) int32 (sx, sy) in [0, 2 pad] or NULL; shift == NULL or pad == 0: no shift.
+ * out: (n, out_h, out_w) contiguous, out_dtype DVLA_DT_BF16 (round to nearest even) or DVLA_DT_F32 (the bits of src), at any
+ * element-aligned address: rows that are not 16-byte aligned get scalar stores in front of and behind their 16-byte body.
+ * n == 0: DVLA_OK.  DVLA_ERR_ARG: src or out null, a size < 1, n < 0, pad < 0.  DVLA_ERR_UNSUPPORTED: another out_dtype,
+ * out_h + out_w > 16384 (the two index tables live in 64 KiB of LDS), src_h or src_w > 2^24, src or out not aligned to its element. */
+int dvla_depth_preprocess(const float* src, const int32_t* shift, void* out, int64_t n, int32_t src_h, int32_t src_w, int32_t out_h,
+                          int32_t out_w, int32_t pad, int32_t out_dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Dreams at evaluation (an addition: the reference decodes its image / depth / feature predictions in mode="train" only).
