@@ -142,6 +142,10 @@ SYMBOLS = {
     "dvla_depth_preprocess": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "dvla_gather_positions": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "dvla_dream_render": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float), _P]),
+    "dvla_image_quality_partial_len": (C.c_int64, [_I64, _I32, _I32]),
+    "dvla_image_quality": (C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _P]),
+    "dvla_depth_quality_partial_len": (C.c_int64, [_I64, _I32, _I32]),
+    "dvla_depth_quality": (C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _P]),
     "dvla_loss_partial_len": (C.c_int64, []),
     "dvla_patch_mse_fwd": (C.c_int, [C.POINTER(FrameView), C.POINTER(FrameView), _P, _I64, _P, _P, _P]),
     "dvla_patch_mse_bwd": (C.c_int, [C.POINTER(FrameView), C.POINTER(FrameView), _P, _I64, _P, C.POINTER(FrameView), _P]),

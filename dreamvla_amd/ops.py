@@ -2119,3 +2119,73 @@ def dream_render(pred, kind, current=None, patch=16):
     check(lib.dvla_dream_render(pred.data_ptr(), _ptr(cur), out.data_ptr(), n, grid, grid, int(patch), ch, m3, s3, _stream()),
           "dvla_dream_render")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# scoring a dream against the frame that arrived (csrc/dream_score.hip): an addition, DESIGN.md section 5 item 18
+# ---------------------------------------------------------------------------------------------------
+def _quality_pair(a, b, what, dtype, tail, names):
+    """the two operands of a quality metric: same shape (..., *tail dims) and `dtype` (ValueError otherwise) -> flattened (n, *tail)
+    views and the leading shape"""
+    for t, nm in ((a, names[0]), (b, names[1])):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}.{nm}: expected a tensor")
+        if t.dtype != dtype:
+            raise ValueError(f"{what}.{nm}: expected {dtype}, got {t.dtype}")
+    if a.dim() < tail or a.shape != b.shape:
+        raise ValueError(f"{what}: two tensors of one shape with at least {tail} dimensions, got {tuple(a.shape)} and {tuple(b.shape)}")
+    return a.reshape(-1, *a.shape[-tail:]), b.reshape(-1, *b.shape[-tail:]), tuple(a.shape[:-tail])
+
+
+def _quality_on_gpu(a, b, what):
+    for t in (a, b):
+        if not t.is_cuda:
+            raise _lib.DvlaError(f"{what}: tensor is on {t.device}; the DreamVLA HIP path has no CPU fallback")
+    return a.contiguous(), b.contiguous()
+
+
+def image_quality(a_u8, b_u8):
+    """How close two batches of uint8 HWC frames (..., h, w, 3) are, per frame, computed on the device in two launches:
+    {"sse": int64 exact sum of squared byte differences, "mse": float32, "psnr": float32 10 log10(255^2 / mse), +inf for identical
+    frames, "ssim": float32 mean SSIM (11 x 11 Gaussian window of sigma 1.5, C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2, population
+    covariances, the (h - 10) x (w - 10) positions whose window lies inside the frame, per channel, averaged: skimage's
+    structural_similarity(gaussian_weights=True, use_sample_covariance=False, data_range=255, channel_axis=-1))}, each of the
+    leading shape: (B, 2, h, w, 3) in, (B, 2) out.  h, w >= 11.  Deterministic: a frame's numbers do not depend on the batch."""
+    a, b, lead = _quality_pair(a_u8, b_u8, "image_quality", torch.uint8, 3, ("a", "b"))
+    n, h, w, c = a.shape
+    if c != 3:
+        raise ValueError(f"image_quality: frames (..., h, w, 3) expected, got {tuple(a_u8.shape)}")
+    if h < 11 or w < 11:
+        raise ValueError(f"image_quality: SSIM's 11 x 11 window does not fit a {h} x {w} frame")
+    a, b = _quality_on_gpu(a, b, "image_quality")
+    lib = _lib.load()
+    sse = torch.empty(n, dtype=torch.int64, device=a.device)
+    f3 = torch.empty((n, 3), dtype=torch.float32, device=a.device)
+    if n:
+        ws = torch.empty(lib.dvla_image_quality_partial_len(n, h, w), dtype=torch.int32, device=a.device)
+        check(lib.dvla_image_quality(a.data_ptr(), b.data_ptr(), n, h, w, sse.data_ptr(), f3.data_ptr(), ws.data_ptr(), _stream()),
+              "dvla_image_quality")
+    return {"sse": sse.view(lead), "mse": f3[:, 0].reshape(lead), "psnr": f3[:, 1].reshape(lead), "ssim": f3[:, 2].reshape(lead)}
+
+
+def depth_quality(pred_f32, target_f32):
+    """The usual depth metrics per map, float32 (..., h, w) both, over the pixels with target > 0 and with p = max(pred, 0):
+    {"valid": int64 number of such pixels, "abs_rel": mean |p - t| / t, "rmse", "silog": losses.silog_loss on those pixels (d =
+    log(t + 1e-6) - log(p + 1e-6), sqrt(mean d^2 - 0.5 mean(d)^2)), "delta1": the share with max(p / t, t / p) < 1.25}, float32,
+    NaN for a map without a valid pixel; each of the leading shape.  Two launches, deterministic."""
+    p, t, lead = _quality_pair(pred_f32, target_f32, "depth_quality", torch.float32, 2, ("pred", "target"))
+    n, h, w = p.shape
+    if h < 1 or w < 1:
+        raise ValueError(f"depth_quality: empty maps {tuple(pred_f32.shape)}")
+    p, t = _quality_on_gpu(p, t, "depth_quality")
+    lib = _lib.load()
+    valid = torch.empty(n, dtype=torch.int64, device=p.device)
+    f4 = torch.empty((n, 4), dtype=torch.float32, device=p.device)
+    if n:
+        ws = torch.empty(lib.dvla_depth_quality_partial_len(n, h, w), dtype=torch.int32, device=p.device)
+        check(lib.dvla_depth_quality(p.data_ptr(), t.data_ptr(), n, h, w, valid.data_ptr(), f4.data_ptr(), ws.data_ptr(), _stream()),
+              "dvla_depth_quality")
+    out = {"valid": valid.view(lead)}
+    for i, k in enumerate(("abs_rel", "rmse", "silog", "delta1")):
+        out[k] = f4[:, i].reshape(lead)
+    return out

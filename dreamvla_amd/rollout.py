@@ -21,6 +21,9 @@ over independent episodes) and removes the redundant work:
   * dreams (opt-in, `dreams=`; an addition -- the reference decodes them in mode="train" only): the decode also runs the requested
     dream heads on the executed position's query rows, which the trunk computes anyway, and renders them (csrc/dream.hip);
     `last_dreams` holds the frame the policy expects next, its depth map and its feature predictions for every control step.
+  * scores of the dreams (opt-in, `score_dreams=`; an addition): `horizon` steps later the predicted frame really arrives; the
+    engine keeps both on the device and scores them there (csrc/dream_score.hip), next to the persistence baseline:
+    `last_dream_scores`.
 
 Episodes of one batch advance in lock-step (one `step` = one control step of every episode); `reset(mask)` restarts
 the episodes selected by a boolean mask (their history is cleared, the others keep theirs).
@@ -78,7 +81,7 @@ class _Graphed:
 
 class RolloutEngine:
     def __init__(self, model, batch_size, history_len=None, use_graph=True, warmup_decodes=3, sample="newest", text="latched",
-                 dreams=()):
+                 dreams=(), score_dreams=False, horizon=3):
         self.model = model.module if hasattr(model, "module") else model
         m = self.model
         if m.training:
@@ -114,6 +117,28 @@ class RolloutEngine:
         self.last_dreams = {}
         self.last_frames_u8 = None              # step_raw: the resized camera frames of the last step, (B, 2, n_px, n_px, 3) uint8
         self.frames = None                      # newest real frame (B, 2, 3, h, w), or the window's (B, S, 2, 3, h, w) with "all"
+        # Scoring the dreams (opt-in, an addition: DESIGN.md section 5 item 18).  The image / depth head predicts the frame `horizon`
+        # control steps ahead (the reference's --future_steps; losses.calvin_losses has the same default), so `horizon` steps after
+        # a dream was made the engine holds both it and the frame it was a dream of: the dream stored `horizon` steps ago is scored
+        # against this step's real frame (ops.image_quality / ops.depth_quality, outside the captured graphs), next to "the frame
+        # stays as it was `horizon` steps ago", the predictor a dream has to beat.  `last_dream_scores` holds the result of the last
+        # step.  Off: no tensors, no launches, the same graphs.
+        self.score_dreams = bool(score_dreams)
+        self.horizon = int(horizon)
+        self._scored = tuple(k for k in ("image", "depth") if k in self.dreams) if self.score_dreams else ()
+        if self.score_dreams:
+            if not self._scored:
+                raise ValueError('score_dreams: "image" or "depth" must be among `dreams` (feature dreams have no target at evaluation)')
+            if sample != "newest":
+                raise ValueError('score_dreams needs sample="newest": one dream per control step')
+            if int(getattr(m, "pred_num", 1)) != 1:
+                raise ValueError("score_dreams needs a model with pred_num == 1")
+            if self.horizon < 1:
+                raise ValueError("horizon: the number of control steps a dream looks ahead, >= 1")
+        self.since_reset = torch.zeros(self.B, dtype=torch.long)    # host: control steps of each episode since its last reset
+        self._score_step = 0                    # control steps scored so far: slot `_score_step % horizon` of the rings is the oldest
+        self._dream_ring = self._frame_ring = self._depth_ring = None   # (B, horizon, 2, n, n, 3) uint8 x 2, (B, horizon, 2, n, n) float32
+        self.last_dream_scores = {}
         # Instruction text.  "latched" = the wrapper's semantics, literally (eval_utils_calvin.py:109-112: `text_queue` is filled
         # once, when it is empty -- i.e. at the first step after `reset()` -- and kept): an episode's instruction is the one it was
         # given at its first step after a reset; a different `text_token` row later is ignored until the next reset.  "current" =
@@ -141,8 +166,11 @@ class RolloutEngine:
         """forget the history of the selected episodes (all when mask is None)"""
         if mask is None:
             self.count.zero_()
+            self.since_reset.zero_()            # a dream made before a reset is never scored against a frame after it
         else:
-            self.count[torch.as_tensor(mask, dtype=torch.bool).cpu()] = 0
+            mask = torch.as_tensor(mask, dtype=torch.bool).cpu()
+            self.count[mask] = 0
+            self.since_reset[mask] = 0
 
     def _encode_eager(self, image_primary, image_wrist, state, text_emb):
         m = self.model
@@ -278,14 +306,20 @@ class RolloutEngine:
         return self.use_graph and self._decode_g.graph is not None and self._encode_g.graph is not None
 
     @torch.no_grad()
-    def step(self, image_primary, image_wrist, state, text_token, noise=None):
+    def step(self, image_primary, image_wrist, state, text_token, noise=None, frames_u8=None, depth_now=None):
         """One control step of every episode.  Returns (action (B, 7) float32 on the device: 6 arm values and the
         gripper command in {-1, +1} as ModelWrapper.step builds it (eval_utils_calvin.py:136-146), arm (B,S,steps,6),
         gripper (B,S,steps,1); with the DiT head and sample="newest" the last two are (B,1,steps,.): the executed position
         only).  `noise`: the DiT sampler's start noise (see draw_noise; a (B*S, steps, 7) draw is accepted with "newest" too --
         the executed position's rows are taken); None = drawn here.
         `text_token`: see `text=` of the constructor -- by default an episode keeps the instruction of its first step after a reset.
-        With `dreams=` the dreams of this step are in `self.last_dreams` afterwards (clones: valid until the caller drops them)."""
+        With `dreams=` the dreams of this step are in `self.last_dreams` afterwards (clones: valid until the caller drops them).
+        With `score_dreams`: `frames_u8` (B, 2, n, n, 3) uint8 are this step's resized camera frames, view 0 = primary (`step_raw`
+        supplies them; required when "image" is scored), `depth_now` (B, 2, n, n) float32 this step's depth maps in the label space
+        (what preprocess.preprocess_depth returns; optional: without it this step has no depth entry); the scores of the dreams
+        made `horizon` steps ago are in `self.last_dream_scores` afterwards (see `_score`)."""
+        if "image" in self._scored and frames_u8 is None:
+            raise ValueError("a scoring engine needs this step's uint8 frames: step(..., frames_u8=(B, 2, n, n, 3)) or step_raw")
         if self.text_mode == "latched":
             fresh = (self.count == 0) if self.tokens is not None else torch.ones(self.B, dtype=torch.bool)
             if self._latched is None or bool(fresh.all()):
@@ -294,12 +328,58 @@ class RolloutEngine:
                 self._latched = torch.where(fresh.to(self.device).view(-1, 1), text_token.to(self.device), self._latched)
             text_token = self._latched
         try:
-            return self._step(image_primary, image_wrist, state, text_token, noise)
+            out = self._step(image_primary, image_wrist, state, text_token, noise)
         except ops.DitTeamTimeout:
             # an EAGER sampler call (warm-up before the capture, or use_graph=False) noticed the timeout itself; the frame was
             # already pushed: fall back and decode this step again
             self._team_fallback()
-            return self._finish_step(noise)
+            out = self._finish_step(noise)
+        if self.score_dreams:
+            self._score(frames_u8, depth_now)
+        return out
+
+    def _score(self, frames_u8, depth_now):
+        """`last_dream_scores` of this step, then this step's dreams (the ones of the decode whose action was returned) and frames
+        take the oldest slot of the rings.
+          "valid"        bool (B,): the episode has run at least `horizon` steps since its last reset -- a dream of THIS episode
+                         exists for this frame
+          "image"        {"sse", "mse", "psnr", "ssim"} (B, 2), view 0 = primary: the dream of `horizon` steps ago against the frame now
+          "persistence"  the same four for the FRAME of `horizon` steps ago against the frame now
+          "depth"        ops.depth_quality's dict, (B, 2); only when `depth_now` was given
+        Rows of episodes that are not valid hold NaN, the integer fields -1."""
+        h = self.horizon
+        slot = self._score_step % h
+        valid = (self.since_reset >= h).to(self.device)
+        scores = {"valid": valid}
+
+        def masked(d):
+            return {k: torch.where(valid.view(-1, 1), v, torch.full_like(v, -1 if v.dtype == torch.int64 else float("nan")))
+                    for k, v in d.items()}
+
+        if "image" in self._scored:
+            dream = self.last_dreams["image"]
+            if not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8 or frames_u8.shape != dream.shape:
+                raise ValueError(f"frames_u8: uint8 {tuple(dream.shape)} expected (the layout of last_dreams['image'])")
+            frames_u8 = frames_u8.to(self.device)
+            if self._dream_ring is None:
+                self._dream_ring = torch.zeros((self.B, h, *dream.shape[1:]), dtype=torch.uint8, device=self.device)
+                self._frame_ring = torch.zeros_like(self._dream_ring)
+            scores["image"] = masked(ops.image_quality(self._dream_ring[:, slot], frames_u8))
+            scores["persistence"] = masked(ops.image_quality(self._frame_ring[:, slot], frames_u8))
+            self._dream_ring[:, slot] = dream
+            self._frame_ring[:, slot] = frames_u8
+        if "depth" in self._scored:
+            dream = self.last_dreams["depth"]
+            if self._depth_ring is None:
+                self._depth_ring = torch.zeros((self.B, h, *dream.shape[1:]), dtype=torch.float32, device=self.device)
+            if depth_now is not None:
+                if not isinstance(depth_now, torch.Tensor) or depth_now.dtype != torch.float32 or depth_now.shape != dream.shape:
+                    raise ValueError(f"depth_now: float32 {tuple(dream.shape)} expected (the layout of last_dreams['depth'])")
+                scores["depth"] = masked(ops.depth_quality(self._depth_ring[:, slot], depth_now.to(self.device)))
+            self._depth_ring[:, slot] = dream
+        self.since_reset += 1
+        self._score_step += 1
+        self.last_dream_scores = scores
 
     def _raw_to_device(self, frames_u8):
         if not isinstance(frames_u8, torch.Tensor):
@@ -312,19 +392,19 @@ class RolloutEngine:
         return frames_u8.to(self.device, non_blocking=True)
 
     @torch.no_grad()
-    def step_raw(self, frames_primary_u8, frames_wrist_u8, state, text_token, noise=None, n_px=224):
+    def step_raw(self, frames_primary_u8, frames_wrist_u8, state, text_token, noise=None, n_px=224, depth_now=None):
         """`step` from the simulator's raw camera frames: (B, h, w, 3) uint8 per camera, host (numpy array or tensor) or device,
         one size per camera.  Upload, CLIP's bicubic Resize + CenterCrop on the device (preprocess.resize_frames_u8: the bytes
         Pillow produces), ToTensor + Normalize + cast (preprocess.preprocess_frames), then `step`: same return value, and the
         same actions bit for bit as `step` on host-resized frames.  The resized frames of this step stay in
         `self.last_frames_u8` (B, 2, n_px, n_px, 3) uint8 on the device, view 0 = primary, 1 = wrist (the layout of
-        `last_dreams["image"]`)."""
+        `last_dreams["image"]`); a scoring engine (`score_dreams`) takes them from here, and `depth_now` as `step` does."""
         from . import preprocess as P
         u8 = torch.stack((P.resize_frames_u8(self._raw_to_device(frames_primary_u8), n_px),
                           P.resize_frames_u8(self._raw_to_device(frames_wrist_u8), n_px)), dim=1)
         x = P.preprocess_frames(u8)                               # (B, 2, 3, n_px, n_px) bf16
         self.last_frames_u8 = u8
-        return self.step(x[:, 0], x[:, 1], state, text_token, noise)
+        return self.step(x[:, 0], x[:, 1], state, text_token, noise, frames_u8=u8 if self.score_dreams else None, depth_now=depth_now)
 
     def _step(self, image_primary, image_wrist, state, text_token, noise):
         dt = self.dtype

@@ -469,6 +469,27 @@ int dvla_gather_positions(const void* x, const int64_t* sel, void* out, int32_t 
                           int32_t tok_begin, int32_t tok_count, void* stream);
 int dvla_dream_render(const void* pred, const void* current, void* out, int64_t n, int32_t grid_h, int32_t grid_w, int32_t patch,
                       int32_t channels, const float* mean3, const float* std3, void* stream);
+/* (additive, ABI 8) Scoring a dream against the frame that arrived (an addition; csrc/dream_score.hip).
+ * Both are two launches -- partials of one tile / chunk each into `partial`, then one workgroup per image adding them in a fixed
+ * order -- without atomics: an image's results are bit-identical from run to run, whatever n and its place in the batch.
+ * `partial`: 4-byte aligned workspace of dvla_*_quality_partial_len(n, height, width) 4-byte words, every word written before read.
+ * dvla_image_quality: a, b (n, height, width, 3) uint8 contiguous at any address.  sse[i] (int64) = the sum of squared byte
+ *   differences of image i, exact.  mse_psnr_ssim (n, 3) fp32 = sse / (3 height width); 10 log10(255^2 / mse), +inf when sse = 0;
+ *   the mean SSIM (Wang et al. 2004): 11 x 11 Gaussian window of sigma 1.5 normalised to sum 1, C1 = (0.01 * 255)^2, C2 =
+ *   (0.03 * 255)^2, population (co)variances, evaluated at the (height - 10) x (width - 10) positions whose window lies inside the
+ *   image, per channel, averaged over positions and channels.  fp32 moments of the pixels centred at 128, the sums of the map
+ *   in float64.  height < 11 or width < 11, or more than 2^31 - 1 tiles: DVLA_ERR_UNSUPPORTED.
+ * dvla_depth_quality: pred, target (n, height, width) fp32 contiguous.  Over the pixels with target > 0, with p = max(pred, 0):
+ *   valid[i] (int64) = their number; metrics4 (n, 4) fp32 = mean |p - t| / t; sqrt(mean (p - t)^2); SiLog with the training loss's
+ *   constants, d = log(t + 1e-6) - log(p + 1e-6), sqrt(mean d^2 - 0.5 mean(d)^2); the share with max(p / t, t / p) < 1.25.
+ *   valid[i] == 0: the four metrics are NaN.
+ * Both: n == 0: DVLA_OK, nothing launched.  DVLA_ERR_ARG: a null pointer, n < 0, a size < 1. */
+int64_t dvla_image_quality_partial_len(int64_t n, int32_t height, int32_t width);
+int dvla_image_quality(const uint8_t* a, const uint8_t* b, int64_t n, int32_t height, int32_t width, int64_t* sse,
+                       float* mse_psnr_ssim, void* partial, void* stream);
+int64_t dvla_depth_quality_partial_len(int64_t n, int32_t height, int32_t width);
+int dvla_depth_quality(const float* pred, const float* target, int64_t n, int32_t height, int32_t width, int64_t* valid,
+                       float* metrics4, void* partial, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * MAE pretraining (models/vit_mae.py:129-256): random masking, the decoder's token un-shuffle and the patch-MSE loss, each
