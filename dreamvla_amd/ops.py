@@ -434,42 +434,64 @@ def gemm(a, b, *, a_trans=False, b_trans=False, bias=None, act=0, want_preact=Fa
     return (out, preact) if want_preact else out
 
 
-def layernorm_fwd(x2, gamma, beta, eps, want_stats):
-    lib = _lib.load()
-    rows, cols = x2.shape
-    y = torch.empty_like(x2)
-    mean = rstd = None
-    if want_stats:
-        mean = torch.empty(rows, dtype=torch.float32, device=x2.device)
-        rstd = torch.empty(rows, dtype=torch.float32, device=x2.device)
+def _ln_param_dt(gamma, beta):
+    """the ONE parameter-dtype code a LayerNorm kernel gets for both of its parameter pointers: weight and bias must agree"""
     pdt = _param_dt(gamma, "layernorm.weight") if gamma is not None else DT_BF16
     if gamma is not None and beta is not None and beta.dtype != gamma.dtype:
         raise TypeError("layernorm weight/bias dtype mismatch")
-    check(lib.dvla_layernorm_fwd(x2.data_ptr(), _ptr(gamma), _ptr(beta), pdt, y.data_ptr(), _ptr(mean), _ptr(rstd),
-                                 rows, cols, float(eps), _stream()), "dvla_layernorm_fwd")
+    return pdt
+
+
+def layernorm_fwd(x, gamma, beta, eps, want_stats, rows=None, cols=None, grp=0, gstride=0, goff=0, map_output=0, out=None):
+    """LayerNorm of `rows` rows of `cols` features of x -> (y, mean, rstd); by default x is (rows, cols).
+    Row groups (include/dvla.h dvla_layernorm_fwd_rows; grp == 0: none): row r is token goff + r % grp of sequence r // grp of an
+    x whose sequences are gstride tokens long; with map_output y (`out`, a buffer of such sequences) is written at that place too."""
+    lib = _lib.load()
+    if rows is None:
+        rows, cols = x.shape
+    y = out if out is not None else torch.empty((rows, cols), dtype=x.dtype, device=x.device)
+    mean = rstd = None
+    if want_stats:
+        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+    check(lib.dvla_layernorm_fwd_rows(x.data_ptr(), _ptr(gamma), _ptr(beta), _ln_param_dt(gamma, beta), y.data_ptr(), _ptr(mean),
+                                      _ptr(rstd), rows, cols, float(eps), grp, gstride, goff, map_output, _stream()),
+          "dvla_layernorm_fwd_rows")
     return y, mean, rstd
 
 
-def layernorm_bwd(dy2, x2, gamma, mean, rstd, need_param_grads, dres2=None, grad_dtype=torch.float32, dg_out=None,
-                  db_out=None, need_dx=True):
-    """dres2: gradient of the residual stream that bypassed the LayerNorm; added to dx inside the kernel.
-    dgamma / dbeta come back in grad_dtype (bf16 or fp32) straight from the reduction kernel.
+def layernorm_bwd(dy, x, gamma, mean, rstd, need_param_grads, dres2=None, grad_dtype=torch.float32, dg_out=None, db_out=None,
+                  need_dx=True, beta=None, want_db=True, rows=None, cols=None, grp=0, gstride=0, goff=0, map_output=0):
+    """-> (dx, dgamma, dbeta); rows / cols and the row groups as in layernorm_fwd (dx is the gradient of the whole of x; with
+    map_output dy is read at the rows' place in a buffer of sequences).
+    dres2: gradient of the residual stream that bypassed the LayerNorm; added to dx inside the kernel (no row groups).
+    dgamma / dbeta come back in grad_dtype (bf16 or fp32) straight from the reduction kernel, written to dg_out / db_out, else to
+    the reducer's slot of gamma / beta (see _grad_dest), else to a fresh vector; want_db=False: no dbeta.
     need_dx=False (with need_param_grads): the input needs no gradient; dx is neither computed nor stored (returns None)."""
     lib = _lib.load()
-    rows, cols = x2.shape
+    if rows is None:
+        rows, cols = x.shape
     if not need_dx and (dres2 is not None or not need_param_grads):
         raise ValueError("layernorm_bwd(need_dx=False) is for parameter gradients only")
-    dx = torch.empty_like(x2) if need_dx else None
+    if grp and dres2 is not None:
+        raise ValueError("layernorm_bwd: no residual gradient with row groups")
+    dx = torch.empty_like(x) if need_dx else None
     dg = db = part = None
     if need_param_grads:
-        dg = dg_out if dg_out is not None else torch.empty(cols, dtype=grad_dtype, device=x2.device)
-        db = db_out if db_out is not None else torch.empty(cols, dtype=grad_dtype, device=x2.device)
-        part = torch.empty(2 * lib.dvla_layernorm_bwd_partial_rows() * cols, dtype=torch.float32, device=x2.device)
-    pdt = _param_dt(gamma, "layernorm.weight") if gamma is not None else DT_BF16
+        dg = dg_out if dg_out is not None else _bias_grad_out(gamma, grad_dtype, cols, x.device)
+        if want_db:
+            db = db_out if db_out is not None else _bias_grad_out(beta, grad_dtype, cols, x.device)
+        part = torch.empty(2 * lib.dvla_layernorm_bwd_partial_rows() * cols, dtype=torch.float32, device=x.device)
+    pdt = _ln_param_dt(gamma, beta)
     gdt = DT_F32 if grad_dtype == torch.float32 else DT_BF16
-    check(lib.dvla_layernorm_bwd_add(dy2.data_ptr(), x2.data_ptr(), _ptr(gamma), pdt, mean.data_ptr(), rstd.data_ptr(),
-                                     _ptr(dres2), _ptr(dx), _ptr(dg), _ptr(db), gdt, _ptr(part), rows, cols, _stream()),
-          "dvla_layernorm_bwd_add")
+    if grp:
+        check(lib.dvla_layernorm_bwd_rows(dy.data_ptr(), x.data_ptr(), _ptr(gamma), pdt, mean.data_ptr(), rstd.data_ptr(), _ptr(dx),
+                                          _ptr(dg), _ptr(db), gdt, _ptr(part), rows, cols, grp, gstride, goff, map_output, _stream()),
+              "dvla_layernorm_bwd_rows")
+    else:
+        check(lib.dvla_layernorm_bwd_add(dy.data_ptr(), x.data_ptr(), _ptr(gamma), pdt, mean.data_ptr(), rstd.data_ptr(),
+                                         _ptr(dres2), _ptr(dx), _ptr(dg), _ptr(db), gdt, _ptr(part), rows, cols, _stream()),
+              "dvla_layernorm_bwd_add")
     return dx, dg, db
 
 
@@ -866,6 +888,16 @@ def _attn_params(q, k, v, o, H, Lq, scale, mt, dropout_p, seed, lse, head_dim=64
     return p
 
 
+def _attn_grad_params(p, dout, dq, dk, dv):
+    """the backward operands of an AttnParams block: the output gradient and the three gradient destinations"""
+    p.dout = dout.data_ptr()
+    p.dq, p.dk, p.dv = dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
+    for name, t in (("do", dout), ("dq", dq), ("dk", dk), ("dv", dv)):
+        setattr(p, name + "_stride_b", t.stride(0))
+        setattr(p, name + "_stride_t", t.stride(1))
+        setattr(p, name + "_stride_h", t.stride(2))
+
+
 def attn_hd_supported(head_dim):
     """head widths of dvla_attn_hd_fwd / _bwd (every width but 64, which has its own kernels): multiples of 8 up to 128"""
     return 8 <= head_dim <= 128 and head_dim % 8 == 0 and head_dim != 64
@@ -896,14 +928,8 @@ def attn_bwd_raw(q, k, v, o, lse, dout, dq, dk, dv, *, scale, mask_tables=None, 
         dout = dout.contiguous()
     p = _attn_params(q, k, v, o, H, Lq, scale, mask_tables, dropout_p, seed, lse, head_dim)
     delta = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
-    p.dout = dout.data_ptr()
-    p.do_stride_b, p.do_stride_t, p.do_stride_h = dout.stride(0), dout.stride(1), dout.stride(2)
+    _attn_grad_params(p, dout, dq, dk, dv)
     p.delta = delta.data_ptr()
-    p.dq, p.dk, p.dv = dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
-    for name, t in (("dq", dq), ("dk", dk), ("dv", dv)):
-        setattr(p, name + "_stride_b", t.stride(0))
-        setattr(p, name + "_stride_t", t.stride(1))
-        setattr(p, name + "_stride_h", t.stride(2))
     if head_dim == 64:
         check(lib.dvla_attn_bwd(C.byref(p), _stream()), "dvla_attn_bwd")
     else:
@@ -1254,36 +1280,48 @@ def mlp(x, w1, b1, w2, b2, *, act, conv1d=False, residual=None, dropout_p=0.0):
                       ACT[act] if isinstance(act, str) else int(act), bool(conv1d), float(dropout_p))
 
 
+def _ln_forward(ctx, x, gamma, beta, eps):
+    """forward of _LayerNorm and _LayerNormFork: LayerNorm(x) in the shape of x"""
+    _req(x, "layernorm.input")
+    cols = x.shape[-1]
+    x2 = x.reshape(-1, cols)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    need_grad = any(ctx.needs_input_grad)
+    y, mean, rstd = layernorm_fwd(x2, gamma, beta, eps, need_grad)
+    ctx.has_affine = gamma is not None
+    ctx.x_shape = x.shape
+    if need_grad:
+        ctx.save_for_backward(x2, gamma, mean, rstd, beta)
+    return y.view(x.shape)
+
+
+def _ln_backward(ctx, dy, dres, need_dx):
+    """backward of _LayerNorm (dres = None) and _LayerNormFork -> (dx, dgamma, dbeta, None).  need_dx=False: an input without
+    gradient (parameter gradients only; where there are none to compute either, dx is computed all the same)"""
+    x2, gamma, mean, rstd, beta = ctx.saved_tensors
+    dy2 = _req(dy, "layernorm.grad_output").reshape(x2.shape)
+    if not dy2.is_contiguous():
+        dy2 = dy2.contiguous()
+    dres2 = None
+    if dres is not None:
+        dres2 = _req(dres, "layernorm.grad_residual").reshape(x2.shape)
+        if not dres2.is_contiguous():
+            dres2 = dres2.contiguous()
+    need_p = ctx.has_affine and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+    dx, dg, db = layernorm_bwd(dy2, x2, gamma, mean, rstd, need_p, dres2, gamma.dtype if need_p else torch.float32,
+                               need_dx=need_dx or not need_p, beta=beta, want_db=beta is not None)
+    return (dx.view(ctx.x_shape) if dx is not None else None), dg, db, None
+
+
 class _LayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, eps):
-        _req(x, "layernorm.input")
-        cols = x.shape[-1]
-        x2 = x.reshape(-1, cols)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
-        need_grad = any(ctx.needs_input_grad)
-        y, mean, rstd = layernorm_fwd(x2, gamma, beta, eps, need_grad)
-        ctx.has_affine = gamma is not None
-        ctx.has_beta = beta is not None
-        ctx.x_shape = x.shape
-        if need_grad:
-            ctx.save_for_backward(x2, gamma, mean, rstd, beta)
-        return y.view(x.shape)
+        return _ln_forward(ctx, x, gamma, beta, eps)
 
     @staticmethod
     def backward(ctx, dy):
-        x2, gamma, mean, rstd, beta = ctx.saved_tensors
-        dy2 = _req(dy, "layernorm.grad_output").reshape(x2.shape)
-        if not dy2.is_contiguous():
-            dy2 = dy2.contiguous()
-        need_p = ctx.has_affine and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
-        gdt = gamma.dtype if need_p else torch.float32
-        need_dx = ctx.needs_input_grad[0] or not need_p       # (an input without gradient: parameter gradients only)
-        dx, dg, db = layernorm_bwd(dy2, x2, gamma, mean, rstd, need_p, None, gdt,
-                                   _grad_dest(gamma, gdt) if need_p else None,
-                                   _grad_dest(beta, gdt) if need_p and ctx.has_beta else None, need_dx=need_dx)
-        return (dx.view(ctx.x_shape) if dx is not None else None), dg, (db if ctx.has_beta else None), None
+        return _ln_backward(ctx, dy, None, ctx.needs_input_grad[0])
 
 
 def layer_norm(x, weight, bias, eps):
@@ -1297,39 +1335,14 @@ class _LayerNormFork(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps):
-        _req(x, "layernorm.input")
-        cols = x.shape[-1]
-        x2 = x.reshape(-1, cols)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
-        need_grad = any(ctx.needs_input_grad)
-        y, mean, rstd = layernorm_fwd(x2, gamma, beta, eps, need_grad)
-        ctx.has_affine = gamma is not None
-        ctx.has_beta = beta is not None
-        ctx.x_shape = x.shape
-        if need_grad:
-            ctx.save_for_backward(x2, gamma, mean, rstd, beta)
-        return x.view_as(x), y.view(x.shape)
+        ctx.set_materialize_grads(False)      # an unused output's gradient arrives as None, not as a tensor of zeros
+        return x.view_as(x), _ln_forward(ctx, x, gamma, beta, eps)
 
     @staticmethod
     def backward(ctx, dres, dy):
-        x2, gamma, mean, rstd, beta = ctx.saved_tensors
         if dy is None:          # the normalised branch was not used
             return dres, None, None, None
-        dy2 = _req(dy, "layernorm.grad_output").reshape(x2.shape)
-        if not dy2.is_contiguous():
-            dy2 = dy2.contiguous()
-        dres2 = None
-        if dres is not None:
-            dres2 = _req(dres, "layernorm.grad_residual").reshape(x2.shape)
-            if not dres2.is_contiguous():
-                dres2 = dres2.contiguous()
-        need_p = ctx.has_affine and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
-        gdt = gamma.dtype if need_p else torch.float32
-        dx, dg, db = layernorm_bwd(dy2, x2, gamma, mean, rstd, need_p, dres2, gdt,
-                                   _grad_dest(gamma, gdt) if need_p else None,
-                                   _grad_dest(beta, gdt) if need_p and ctx.has_beta else None)
-        return dx.view(ctx.x_shape), dg, (db if ctx.has_beta else None), None
+        return _ln_backward(ctx, dy, dres, True)
 
 
 class _LayerNormRows(torch.autograd.Function):
@@ -1339,51 +1352,29 @@ class _LayerNormRows(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, keep):
-        lib = _lib.load()
         _req(x, "layernorm.input")
         n, L, D = x.shape
         if not x.is_contiguous():
             x = x.contiguous()
         need_grad = any(ctx.needs_input_grad)
-        rows = n * keep
-        y = torch.empty((rows, D), dtype=x.dtype, device=x.device)
-        mean = rstd = None
-        if need_grad:
-            mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-            rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-        pdt = _param_dt(gamma, "layernorm.weight") if gamma is not None else DT_BF16
-        check(lib.dvla_layernorm_fwd_rows(x.data_ptr(), _ptr(gamma), _ptr(beta), pdt, y.data_ptr(), _ptr(mean), _ptr(rstd),
-                                          rows, D, float(eps), keep, L, L - keep, 0, _stream()), "dvla_layernorm_fwd_rows")
-        ctx.keep, ctx.has_affine, ctx.has_beta = keep, gamma is not None, beta is not None
+        y, mean, rstd = layernorm_fwd(x, gamma, beta, eps, need_grad, n * keep, D, keep, L, L - keep)
+        ctx.keep, ctx.has_affine = keep, gamma is not None
         if need_grad:
             ctx.save_for_backward(x, gamma, mean, rstd, beta)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        lib = _lib.load()
         x, gamma, mean, rstd, beta = ctx.saved_tensors
         n, L, D = x.shape
         keep = ctx.keep
-        rows = n * keep
-        dy2 = _req(dy, "layernorm.grad_output").reshape(rows, D)
+        dy2 = _req(dy, "layernorm.grad_output").reshape(n * keep, D)
         if not dy2.is_contiguous():
             dy2 = dy2.contiguous()
         need_p = ctx.has_affine and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
-        gdt = gamma.dtype if need_p else torch.float32
-        dx = torch.empty_like(x)
-        dg = db = part = None
-        if need_p:
-            dg = _grad_dest(gamma, gdt)
-            db = _grad_dest(beta, gdt) if ctx.has_beta else None
-            dg = dg if dg is not None else torch.empty(D, dtype=gdt, device=x.device)
-            db = db if (db is not None or not ctx.has_beta) else torch.empty(D, dtype=gdt, device=x.device)
-            part = torch.empty(2 * lib.dvla_layernorm_bwd_partial_rows() * D, dtype=torch.float32, device=x.device)
-        pdt = _param_dt(gamma, "layernorm.weight") if gamma is not None else DT_BF16
-        check(lib.dvla_layernorm_bwd_rows(dy2.data_ptr(), x.data_ptr(), _ptr(gamma), pdt, mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
-                                          _ptr(dg), _ptr(db), DT_F32 if gdt == torch.float32 else DT_BF16, _ptr(part), rows, D,
-                                          keep, L, L - keep, 0, _stream()), "dvla_layernorm_bwd_rows")
-        return dx, dg, (db if ctx.has_beta else None), None, None
+        dx, dg, db = layernorm_bwd(dy2, x, gamma, mean, rstd, need_p, None, gamma.dtype if need_p else torch.float32, beta=beta,
+                                   want_db=beta is not None, rows=n * keep, cols=D, grp=keep, gstride=L, goff=L - keep)
+        return dx, dg, db, None, None
 
 
 class _LayerNormConcat(torch.autograd.Function):
@@ -1394,38 +1385,28 @@ class _LayerNormConcat(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a, ga, ba, b, gb, bb, eps_a, eps_b):
-        lib = _lib.load()
         _req(a, "layernorm.input"); _req(b, "layernorm.input")
         n, La, D = a.shape
         Lb = b.shape[1]
         if b.shape[0] != n or b.shape[2] != D:
             raise ValueError("layer_norm_concat: (n, La, D) and (n, Lb, D)")
+        _ln_param_dt(gb, bb)          # (b's parameters are refused before a's launch, not after it)
         a = a if a.is_contiguous() else a.contiguous()
         b = b if b.is_contiguous() else b.contiguous()
         L = La + Lb
         out = torch.empty((n, L, D), dtype=a.dtype, device=a.device)
         need_grad = any(ctx.needs_input_grad)
-        stats = []
-        for (x, g, be, Lx, off, eps) in ((a, ga, ba, La, 0, eps_a), (b, gb, bb, Lb, La, eps_b)):
-            rows = n * Lx
-            mean = torch.empty(rows, dtype=torch.float32, device=a.device) if need_grad else None
-            rstd = torch.empty(rows, dtype=torch.float32, device=a.device) if need_grad else None
-            pdt = _param_dt(g, "layernorm.weight") if g is not None else DT_BF16
-            check(lib.dvla_layernorm_fwd_rows(x.data_ptr(), _ptr(g), _ptr(be), pdt, out.data_ptr(), _ptr(mean), _ptr(rstd), rows, D, float(eps),
-                                              Lx, L, off, 1, _stream()), "dvla_layernorm_fwd_rows")
-            stats += [mean, rstd]
+        _, mean_a, rstd_a = layernorm_fwd(a, ga, ba, eps_a, need_grad, n * La, D, La, L, 0, 1, out)
+        _, mean_b, rstd_b = layernorm_fwd(b, gb, bb, eps_b, need_grad, n * Lb, D, Lb, L, La, 1, out)
         ctx.dims = (n, La, Lb, D)
-        ctx.flags = (ga is not None, ba is not None, gb is not None, bb is not None)
         if need_grad:
-            ctx.save_for_backward(a, ga, ba, b, gb, bb, *stats)
+            ctx.save_for_backward(a, ga, ba, b, gb, bb, mean_a, rstd_a, mean_b, rstd_b)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        lib = _lib.load()
         a, ga, ba, b, gb, bb, mean_a, rstd_a, mean_b, rstd_b = ctx.saved_tensors
         n, La, Lb, D = ctx.dims
-        L = La + Lb
         dout = _req(dout, "layernorm.grad_output")
         dout = dout if dout.is_contiguous() else dout.contiguous()
         res = []
@@ -1435,23 +1416,10 @@ class _LayerNormConcat(torch.autograd.Function):
             if not (need_x or need_p):
                 res += [None, None, None]
                 continue
-            rows = n * Lx
-            gdt = g.dtype if need_p else torch.float32
-            dx = torch.empty_like(x) if need_x else None      # (no input gradient wanted: neither reduced nor stored)
-            dg = db = part = None
-            if need_p:
-                dg = _grad_dest(g, gdt)
-                dg = dg if dg is not None else torch.empty(D, dtype=gdt, device=x.device)
-                if be is not None:
-                    db = _grad_dest(be, gdt)
-                    db = db if db is not None else torch.empty(D, dtype=gdt, device=x.device)
-                part = torch.empty(2 * lib.dvla_layernorm_bwd_partial_rows() * D, dtype=torch.float32, device=x.device)
-            pdt = _param_dt(g, "layernorm.weight") if g is not None else DT_BF16
-            check(lib.dvla_layernorm_bwd_rows(dout.data_ptr(), x.data_ptr(), _ptr(g), pdt, mean.data_ptr(), rstd.data_ptr(), _ptr(dx),
-                                              _ptr(dg), _ptr(db), DT_F32 if gdt == torch.float32 else DT_BF16, _ptr(part), rows, D,
-                                              Lx, L, off, 1, _stream()), "dvla_layernorm_bwd_rows")
-            res += [dx, dg, db]
-        return (*res[:3], *res[3:], None, None)
+            # (no input gradient wanted: neither reduced nor stored)
+            res += layernorm_bwd(dout, x, g, mean, rstd, need_p, None, g.dtype if need_p else torch.float32, need_dx=need_x, beta=be,
+                                 want_db=be is not None, rows=n * Lx, cols=D, grp=Lx, gstride=La + Lb, goff=off, map_output=1)
+        return (*res, None, None)
 
 
 def layer_norm_concat(a, wa, ba, eps_a, b, wb, bb, eps_b):
@@ -1467,8 +1435,6 @@ def layer_norm_last_tokens(x, weight, bias, eps, keep):
     x = to_compute(x)
     if x.dim() != 3 or not (0 < keep <= x.shape[1]) or x.shape[-1] % 8 != 0 or x.shape[-1] > 2048:
         raise ValueError("layer_norm_last_tokens: x (n, L, D) with D % 8 == 0, D <= 2048 and 0 < keep <= L")
-    if weight is not None and bias is not None and bias.dtype != weight.dtype:
-        raise TypeError("layernorm weight/bias dtype mismatch")
     return _LayerNormRows.apply(x, weight, bias, float(eps), int(keep))
 
 
@@ -1481,113 +1447,11 @@ def layer_norm_fork(x, weight, bias, eps):
 
 
 class _SelfAttention(torch.autograd.Function):
-    """Packed self-attention: qkv (B, L, 3*H*64) laid out [q | k | v] x (H, 64) -- exactly timm's
-    qkv.reshape(B,N,3,h,d) and GPT-2's c_attn(...).split(H) order.  Returns (B, L, H*64)."""
-
-    @staticmethod
-    def forward(ctx, qkv, H, scale, mask_tables, dropout_p):
-        _req(qkv, "attention.qkv")
-        B, L, W = qkv.shape
-        if W != 3 * H * 64:
-            raise ValueError("attention: head_dim must be 64")
-        if not qkv.is_contiguous():
-            qkv = qkv.contiguous()
-        v5 = qkv.view(B, L, 3, H, 64)
-        q, k, v = v5[:, :, 0], v5[:, :, 1], v5[:, :, 2]
-        need_grad = any(ctx.needs_input_grad)
-        seed = next_seed() if dropout_p > 0 else (0, 0)
-        o, lse = attn_fwd_raw(q, k, v, scale=scale, mask_tables=mask_tables, dropout_p=dropout_p, seed=seed,
-                              want_lse=need_grad)
-        ctx.H, ctx.scale, ctx.dropout_p, ctx.seed, ctx.mt = H, scale, dropout_p, seed, mask_tables
-        if need_grad:
-            ctx.save_for_backward(qkv, o, lse)
-        return o.view(B, L, H * 64)
-
-    @staticmethod
-    def backward(ctx, dout):
-        qkv, o, lse = ctx.saved_tensors
-        B, L, _ = qkv.shape
-        H, mt = ctx.H, ctx.mt
-        v5 = qkv.view(B, L, 3, H, 64)
-        # with a compacted key axis the kernel leaves dk/dv rows of never-visible keys untouched -> zeros
-        dead = getattr(mt, "dead_keys", None) if mt is not None else None
-        if mt is not None and mt.key_index is not None and dead is None:
-            dqkv = torch.zeros_like(qkv)             # tables built on the device: the unnamed rows are not listed
-        else:
-            dqkv = torch.empty_like(qkv)
-            if dead is not None and dead.numel():
-                # dk / dv of the never-visible keys (a few rows, not the buffer); index_fill_, not `[...] = 0`: the indexed
-                # assignment uploads its scalar from the host every call (a copy + 60 us of idle GPU per layer)
-                dqkv.view(B, L, 3, H * 64)[:, :, 1:].index_fill_(1, dead, 0)
-        d5 = dqkv.view(B, L, 3, H, 64)
-        do = _req(dout, "attention.grad_output").contiguous().view(B, L, H, 64)
-        attn_bwd_raw(v5[:, :, 0], v5[:, :, 1], v5[:, :, 2], o, lse, do, d5[:, :, 0], d5[:, :, 1], d5[:, :, 2],
-                     scale=ctx.scale, mask_tables=mt, dropout_p=ctx.dropout_p, seed=ctx.seed)
-        return dqkv, None, None, None, None
-
-
-class _SelfAttentionSmall(torch.autograd.Function):
-    """Packed self-attention with head_dim != 64 on short sequences (dvla_attn_small_fwd / _bwd: L <= 64, head_dim <= 128, no
-    mask, no dropout) -- the DiT-S action head (head_dim 96, 6 tokens).  qkv (B, L, 3*H*D) -> (B, L, H*D)."""
-
-    @staticmethod
-    def forward(ctx, qkv, H, D, scale):
-        lib = _lib.load()
-        _req(qkv, "attention.qkv")
-        B, L, W = qkv.shape
-        if W != 3 * H * D:
-            raise ValueError("attention: qkv width must be 3 * heads * head_dim")
-        if L > 64 or D > 128 or D % 8 or (4 * L * (D + 1) + 2 * L * (L + 1)) * 4 > 160 * 1024 or B > 65535:
-            raise _lib.DvlaError(f"attention with head_dim {D}: only sequences of <= 64 tokens and head_dim <= 128 (multiple of 8) "
-                                 f"are supported off the head_dim-64 MFMA kernels (got L = {L})")
-        if not qkv.is_contiguous():
-            qkv = qkv.contiguous()
-        v5 = qkv.view(B, L, 3, H, D)
-        o = torch.empty((B, L, H, D), dtype=BF16, device=qkv.device)
-        lse = torch.empty((B, H, L), dtype=torch.float32, device=qkv.device)
-        p = _SelfAttentionSmall._params(v5[:, :, 0], v5[:, :, 1], v5[:, :, 2], o, H, L, scale, lse)
-        check(lib.dvla_attn_small_fwd(C.byref(p), D, _stream()), "dvla_attn_small_fwd")
-        ctx.H, ctx.D, ctx.scale = H, D, scale
-        if any(ctx.needs_input_grad):
-            ctx.save_for_backward(qkv, o, lse)
-        return o.view(B, L, H * D)
-
-    @staticmethod
-    def _params(q, k, v, o, H, L, scale, lse):
-        p = AttnParams()
-        p.q, p.k, p.v, p.o = q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr()
-        for name, t in (("q", q), ("k", k), ("v", v), ("o", o)):
-            setattr(p, name + "_stride_b", t.stride(0)); setattr(p, name + "_stride_t", t.stride(1)); setattr(p, name + "_stride_h", t.stride(2))
-        p.B, p.H, p.Lq, p.Lk = q.shape[0], H, L, L
-        p.scale = float(scale)
-        p.lse = lse.data_ptr()
-        return p
-
-    @staticmethod
-    def backward(ctx, dout):
-        lib = _lib.load()
-        qkv, o, lse = ctx.saved_tensors
-        B, L, _ = qkv.shape
-        H, D = ctx.H, ctx.D
-        v5 = qkv.view(B, L, 3, H, D)
-        dqkv = torch.empty_like(qkv)
-        d5 = dqkv.view(B, L, 3, H, D)
-        do = _req(dout, "attention.grad_output").contiguous().view(B, L, H, D)
-        p = _SelfAttentionSmall._params(v5[:, :, 0], v5[:, :, 1], v5[:, :, 2], o, H, L, ctx.scale, lse)
-        p.dout = do.data_ptr()
-        p.do_stride_b, p.do_stride_t, p.do_stride_h = do.stride(0), do.stride(1), do.stride(2)
-        p.dq, p.dk, p.dv = d5[:, :, 0].data_ptr(), d5[:, :, 1].data_ptr(), d5[:, :, 2].data_ptr()
-        for name, t in (("dq", d5[:, :, 0]), ("dk", d5[:, :, 1]), ("dv", d5[:, :, 2])):
-            setattr(p, name + "_stride_b", t.stride(0)); setattr(p, name + "_stride_t", t.stride(1)); setattr(p, name + "_stride_h", t.stride(2))
-        check(lib.dvla_attn_small_bwd(C.byref(p), D, _stream()), "dvla_attn_small_bwd")
-        return dqkv, None, None, None
-
-
-class _SelfAttentionHD(torch.autograd.Function):
-    """Packed self-attention with head_dim D != 64 (attn_hd_supported) at any length, with masks and dropout
-    (dvla_attn_hd_fwd / _bwd): the trunk of a model whose hidden_dim / transformer_heads is not 64 and the 16-head dream-head
-    decoders of any hidden_dim != 1024.  qkv (B, L, 3*H*D) -> (B, L, H*D); same tables, seeds and zero-fill rules as
-    _SelfAttention."""
+    """Packed self-attention: qkv (B, L, 3*H*D) laid out [q | k | v] x (H, D) -- exactly timm's qkv.reshape(B,N,3,h,d) and GPT-2's
+    c_attn(...).split(H) order.  Returns (B, L, H*D).  D = 64: the MFMA kernels (dvla_attn_fwd / _bwd); any other D
+    (attn_hd_supported) the head-width-generic ones (dvla_attn_hd_fwd / _bwd), at any length, with masks and dropout: the trunk
+    of a model whose hidden_dim / transformer_heads is not 64 and the 16-head dream-head decoders of any hidden_dim != 1024.
+    Same tables, seeds and zero-fill rule for both (attn_fwd_raw / attn_bwd_raw choose by head_dim)."""
 
     @staticmethod
     def forward(ctx, qkv, H, D, scale, mask_tables, dropout_p):
@@ -1613,12 +1477,15 @@ class _SelfAttentionHD(torch.autograd.Function):
         B, L, _ = qkv.shape
         H, D, mt = ctx.H, ctx.D, ctx.mt
         v5 = qkv.view(B, L, 3, H, D)
+        # with a compacted key axis the kernel leaves dk/dv rows of never-visible keys untouched -> zeros
         dead = getattr(mt, "dead_keys", None) if mt is not None else None
         if mt is not None and mt.key_index is not None and dead is None:
-            dqkv = torch.zeros_like(qkv)
+            dqkv = torch.zeros_like(qkv)             # tables built on the device: the unnamed rows are not listed
         else:
             dqkv = torch.empty_like(qkv)
             if dead is not None and dead.numel():
+                # dk / dv of the never-visible keys (a few rows, not the buffer); index_fill_, not `[...] = 0`: the indexed
+                # assignment uploads its scalar from the host every call (a copy + 60 us of idle GPU per layer)
                 dqkv.view(B, L, 3, H * D)[:, :, 1:].index_fill_(1, dead, 0)
         d5 = dqkv.view(B, L, 3, H, D)
         do = _req(dout, "attention.grad_output").contiguous().view(B, L, H, D)
@@ -1630,6 +1497,48 @@ class _SelfAttentionHD(torch.autograd.Function):
 def _small_attention_fits(B, L, D):
     """the shapes _SelfAttentionSmall takes (its kernel's limits, include/dvla.h)"""
     return L <= 64 and D <= 128 and D % 8 == 0 and (4 * L * (D + 1) + 2 * L * (L + 1)) * 4 <= 160 * 1024 and B <= 65535
+
+
+class _SelfAttentionSmall(torch.autograd.Function):
+    """Packed self-attention with head_dim != 64 on short sequences (dvla_attn_small_fwd / _bwd: _small_attention_fits, no
+    mask, no dropout) -- the DiT-S action head (head_dim 96, 6 tokens).  qkv (B, L, 3*H*D) -> (B, L, H*D)."""
+
+    @staticmethod
+    def forward(ctx, qkv, H, D, scale):
+        lib = _lib.load()
+        _req(qkv, "attention.qkv")
+        B, L, W = qkv.shape
+        if W != 3 * H * D:
+            raise ValueError("attention: qkv width must be 3 * heads * head_dim")
+        if not _small_attention_fits(B, L, D):
+            raise _lib.DvlaError(f"attention with head_dim {D}: only sequences of <= 64 tokens and head_dim <= 128 (multiple of 8) "
+                                 f"are supported off the head_dim-64 MFMA kernels (got L = {L})")
+        if not qkv.is_contiguous():
+            qkv = qkv.contiguous()
+        v5 = qkv.view(B, L, 3, H, D)
+        o = torch.empty((B, L, H, D), dtype=BF16, device=qkv.device)
+        lse = torch.empty((B, H, L), dtype=torch.float32, device=qkv.device)
+        p = _attn_params(v5[:, :, 0], v5[:, :, 1], v5[:, :, 2], o, H, L, scale, mt=None, dropout_p=0.0, seed=(0, 0), lse=lse, head_dim=D)
+        check(lib.dvla_attn_small_fwd(C.byref(p), D, _stream()), "dvla_attn_small_fwd")
+        ctx.H, ctx.D, ctx.scale = H, D, scale
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(qkv, o, lse)
+        return o.view(B, L, H * D)
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        qkv, o, lse = ctx.saved_tensors
+        B, L, _ = qkv.shape
+        H, D = ctx.H, ctx.D
+        v5 = qkv.view(B, L, 3, H, D)
+        dqkv = torch.empty_like(qkv)
+        d5 = dqkv.view(B, L, 3, H, D)
+        do = _req(dout, "attention.grad_output").contiguous().view(B, L, H, D)
+        p = _attn_params(v5[:, :, 0], v5[:, :, 1], v5[:, :, 2], o, H, L, ctx.scale, mt=None, dropout_p=0.0, seed=(0, 0), lse=lse, head_dim=D)
+        _attn_grad_params(p, do, d5[:, :, 0], d5[:, :, 1], d5[:, :, 2])      # (`delta` stays unset: the short kernel takes none)
+        check(lib.dvla_attn_small_bwd(C.byref(p), D, _stream()), "dvla_attn_small_bwd")
+        return dqkv, None, None, None
 
 
 _PACK_TABLES = {}
@@ -1650,7 +1559,7 @@ def _packed_block_diagonal(G, L, device):
 def self_attention(qkv, num_heads, *, scale=None, mask_tables=None, dropout_p=0.0, head_dim=64):
     """qkv (B, L, 3 * H * D) -> (B, L, H * D).  head_dim 64: the kernels below.  Any other head_dim: short sequences without
     mask or dropout take the short-sequence kernel (_SelfAttentionSmall: the DiT-S head), everything else the head-width-generic
-    kernels (_SelfAttentionHD: multiples of 8 up to 128).
+    kernels (_SelfAttention with that head_dim: multiples of 8 up to 128).
     Very short sequences (the DiT action head: L = 6, B = 1792) are PACKED: G consecutive sequences are handed to the
     kernels as one sequence of G * L tokens under a block-diagonal mask (a view -- the batch is contiguous -- plus a cached
     table): the kernels work on 32 x 32 score tiles and 128-query workgroups, so one 6 x 6 problem per workgroup used
@@ -1665,16 +1574,16 @@ def self_attention(qkv, num_heads, *, scale=None, mask_tables=None, dropout_p=0.
         if not attn_hd_supported(head_dim):
             raise _lib.DvlaError(f"attention with head_dim {head_dim}: supported head widths are 64 and the multiples of 8 "
                                  f"from 8 to 128")
-        return _SelfAttentionHD.apply(qkv, int(num_heads), int(head_dim), float(scale), mask_tables, float(dropout_p))
+        return _SelfAttention.apply(qkv, int(num_heads), int(head_dim), float(scale), mask_tables, float(dropout_p))
     if mask_tables is None and dropout_p == 0.0 and 1 < L <= 16 and B >= 64 and qkv.is_contiguous():
         G = 128 // L
         while G > 1 and B % G != 0:
             G -= 1
         if G > 1:
             mt = _packed_block_diagonal(G, L, qkv.device)
-            o = _SelfAttention.apply(qkv.view(B // G, G * L, qkv.shape[2]), int(num_heads), float(scale), mt, 0.0)
+            o = _SelfAttention.apply(qkv.view(B // G, G * L, qkv.shape[2]), int(num_heads), 64, float(scale), mt, 0.0)
             return o.view(B, L, o.shape[2])
-    return _SelfAttention.apply(qkv, int(num_heads), float(scale), mask_tables, float(dropout_p))
+    return _SelfAttention.apply(qkv, int(num_heads), 64, float(scale), mask_tables, float(dropout_p))
 
 
 class _CrossAttention(torch.autograd.Function):

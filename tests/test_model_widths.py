@@ -91,11 +91,13 @@ def test_trunk_refuses_unsupported_head_widths_and_names_the_set(hidden, heads):
 
 
 def _route(monkeypatch, B, L, D, H=2, mask_tables=None, dropout_p=0.0):
-    """which autograd Function ops.self_attention hands a (B, L, 3 H D) problem to (no kernel runs)"""
+    """which autograd Function ops.self_attention hands a (B, L, 3 H D) problem to, and the head_dim it hands over -- both
+    Functions take (qkv, heads, head_dim, ...); _SelfAttention with 64 is the MFMA kernel family, with any other width the
+    head-width-generic one (test_raw_launchers_pick_the_kernel_family_from_head_dim below).  No kernel runs."""
     from dreamvla_amd import ops
     seen = []
-    for name in ("_SelfAttention", "_SelfAttentionSmall", "_SelfAttentionHD"):
-        monkeypatch.setattr(getattr(ops, name), "apply", staticmethod(lambda *a, _n=name: seen.append(_n)))
+    for name in ("_SelfAttention", "_SelfAttentionSmall"):
+        monkeypatch.setattr(getattr(ops, name), "apply", staticmethod(lambda *a, _n=name: seen.append((_n, a[2]))))
     monkeypatch.setattr(ops, "to_compute", lambda x: x)
     ops.self_attention(torch.zeros(B, L, 3 * H * D, dtype=torch.bfloat16), H, scale=1.0 / math.sqrt(D),
                        mask_tables=mask_tables, dropout_p=dropout_p, head_dim=D)
@@ -103,17 +105,40 @@ def _route(monkeypatch, B, L, D, H=2, mask_tables=None, dropout_p=0.0):
 
 
 def test_routing_keeps_head_width_64_and_the_short_kernel(monkeypatch):
-    assert _route(monkeypatch, 2, 205, 64) == ["_SelfAttention"]
-    assert _route(monkeypatch, 1792, 6, 96) == ["_SelfAttentionSmall"]         # DiT-S: unchanged
-    assert _route(monkeypatch, 4, 64, 24) == ["_SelfAttentionSmall"]
+    assert _route(monkeypatch, 2, 205, 64) == [("_SelfAttention", 64)]
+    assert _route(monkeypatch, 1792, 6, 96) == [("_SelfAttentionSmall", 96)]   # DiT-S: unchanged
+    assert _route(monkeypatch, 4, 64, 24) == [("_SelfAttentionSmall", 24)]
 
 
 def test_routing_sends_what_raised_before_to_the_generic_kernels(monkeypatch):
-    assert _route(monkeypatch, 1, 205, 24) == ["_SelfAttentionHD"]             # W decoder
-    assert _route(monkeypatch, 1, 265, 48) == ["_SelfAttentionHD"]             # V decoder
-    assert _route(monkeypatch, 1, 40, 32, dropout_p=0.1) == ["_SelfAttentionHD"]
-    assert _route(monkeypatch, 1, 64, 128) == ["_SelfAttentionHD"]             # over the short kernel's LDS
-    assert _route(monkeypatch, 1, 40, 32, mask_tables=object()) == ["_SelfAttentionHD"]
+    assert _route(monkeypatch, 1, 205, 24) == [("_SelfAttention", 24)]         # W decoder
+    assert _route(monkeypatch, 1, 265, 48) == [("_SelfAttention", 48)]         # V decoder
+    assert _route(monkeypatch, 1, 40, 32, dropout_p=0.1) == [("_SelfAttention", 32)]
+    assert _route(monkeypatch, 1, 64, 128) == [("_SelfAttention", 128)]        # over the short kernel's LDS
+    assert _route(monkeypatch, 1, 40, 32, mask_tables=object()) == [("_SelfAttention", 32)]
+
+
+def test_raw_launchers_pick_the_kernel_family_from_head_dim(monkeypatch):
+    """attn_fwd_raw / attn_bwd_raw: dvla_attn_fwd / _bwd for head_dim 64 only, dvla_attn_hd_fwd / _bwd (with the width) for every
+    other -- what makes the head_dim of _route the kernel family.  Library, tensor checks and parameter block are stubs."""
+    from dreamvla_amd import _lib, ops
+    calls = []
+
+    class Lib:
+        def __getattr__(self, name):
+            return lambda *a: calls.append((name, a[1] if len(a) == 3 else None)) or 0
+
+    monkeypatch.setattr(_lib, "load", lambda: Lib())
+    monkeypatch.setattr(ops, "_req", lambda t, *a, **k: t)
+    monkeypatch.setattr(ops, "_attn_params", lambda *a, **k: _lib.AttnParams())
+    monkeypatch.setattr(ops, "_stream", lambda: 0)
+    for D in (8, 24, 32, 48, 56, 64, 72, 96, 128):
+        q = torch.zeros(1, 5, 2, D, dtype=torch.bfloat16)
+        del calls[:]
+        o, lse = ops.attn_fwd_raw(q, q, q, scale=1.0, head_dim=D)
+        ops.attn_bwd_raw(q, q, q, o, lse, o, *(torch.empty_like(q) for _ in range(3)), scale=1.0, head_dim=D)
+        assert calls == ([("dvla_attn_fwd", None), ("dvla_attn_bwd", None)] if D == 64 else
+                         [("dvla_attn_hd_fwd", D), ("dvla_attn_hd_bwd", D)]), (D, calls)
 
 
 @pytest.mark.parametrize("D", [12, 136])
