@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DVLA_LIB") or os.path.join(_HERE, "libdvla_hip.so")
 
 DT_BF16, DT_F32 = 0, 1
+CROP_OUT_U8, CROP_OUT_BF16 = 0, 1      # DVLA_CROP_OUT_* of include/dvla.h (dvla_image_resized_crop's out_kind)
 ABI_VERSION = 8          # DVLA_ABI_VERSION of include/dvla.h
 ACT = {"none": 0, "gelu": 1, "gelu_erf": 1, "gelu_tanh": 2, "gelu_new": 2, "relu": 3, "silu": 4,
        "quick_gelu": 5, "tanh": 6, "sigmoid": 7}
@@ -139,6 +140,8 @@ SYMBOLS = {
     "dvla_mask_tables": (C.c_int, [C.POINTER(MaskRule), _P, _P, _P, _P, _P, _P]),
     "dvla_image_preprocess": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float), _P]),
     "dvla_image_resize_u8": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _I32, _I32, _I32, _I32, _P]),
+    "dvla_image_resized_crop": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _I32, C.POINTER(C.c_float),
+                                          C.POINTER(C.c_float), _P]),
     "dvla_depth_preprocess": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "dvla_gather_positions": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "dvla_dream_render": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float), _P]),

@@ -13,6 +13,11 @@ torchvision's Resize / CenterCrop on a PIL image are `Image.resize((w', h'), BIC
 tables are built here on the host exactly as Pillow builds them (`bicubic_tables`) and the kernel does integer arithmetic only;
 `resize_u8_reference` is the same integer arithmetic in numpy, the host mirror of the kernel.
 
+`resized_crop_u8` / `resized_crop` are MAE's augmentation on the device (csrc/image_resized_crop.hip): a crop box per frame
+(`draw_resized_crops`), each crop resized to n_px x n_px with the same arithmetic on the tables of ITS size pair out of a
+device-resident store of every size's tables, an optional horizontal flip, and ToTensor + Normalize + the bf16 cast fused in;
+`resized_crop_u8_reference` is the host mirror.
+
 `preprocess_depth` is the depth labels' counterpart of `preprocess_frames` (csrc/depth_pipeline.hip): the collator's nearest resize
 of the raw fp32 depth maps, the shift gather and the cast in one kernel; `depth_resize_reference` is its host mirror."""
 import functools
@@ -202,6 +207,159 @@ def resize_frames_u8(frames_u8, n_px=224):
     _lib.check(lib.dvla_image_resize_u8(src.data_ptr(), out.data_ptr(), n, h, w, nh, nw, bx.data_ptr(), kx.data_ptr(), ksx,
                                         by.data_ptr(), ky.data_ptr(), ksy, left, top, int(n_px), _stream()), "dvla_image_resize_u8")
     return out.view(*lead, n_px, n_px, 3)
+
+
+def draw_resized_crops(n, h, w, scale=(0.2, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), p_flip=0.5, generator=None):
+    """(n, 5) int32 CPU tensor of (top, left, ch, cw, flip): the boxes of torchvision's RandomResizedCrop.get_params and the coin of
+    RandomHorizontalFlip for n frames of h x w, vectorised over n.  Ten attempts per frame, each with an area of h w U(scale) and an
+    aspect ratio of exp(U(log ratio)), cw = round(sqrt(area ratio)), ch = round(sqrt(area / ratio)); the first attempt that fits the
+    frame is taken at a uniform integer offset; a frame without one gets the central crop with the frame's ratio clamped to
+    `ratio`.  The algorithm is torchvision's, the random stream is this function's own."""
+    n, h, w = int(n), int(h), int(w)
+    if n < 0 or h < 1 or w < 1:
+        raise ValueError("draw_resized_crops: n >= 0 frames of at least 1 x 1 expected")
+    if not (0.0 < scale[0] <= scale[1] and 0.0 < ratio[0] <= ratio[1] and 0.0 <= p_flip <= 1.0):
+        raise ValueError("draw_resized_crops: 0 < scale[0] <= scale[1], 0 < ratio[0] <= ratio[1], 0 <= p_flip <= 1 expected")
+    u = torch.rand(4, n, 10, generator=generator, dtype=torch.float64)
+    area = (h * w) * (scale[0] + (scale[1] - scale[0]) * u[0])
+    log_r = (math.log(ratio[0]), math.log(ratio[1]))
+    ar = torch.exp(log_r[0] + (log_r[1] - log_r[0]) * u[1])
+    cw = torch.round(torch.sqrt(area * ar)).long()
+    ch = torch.round(torch.sqrt(area / ar)).long()
+    ok = (cw > 0) & (cw <= w) & (ch > 0) & (ch <= h)
+    first = ok.int().argmax(dim=1, keepdim=True)                       # the first attempt that fits (0 where none does)
+    found = ok.any(dim=1)
+    cw, ch = cw.gather(1, first)[:, 0], ch.gather(1, first)[:, 0]
+    top = (u[2].gather(1, first)[:, 0] * (h - ch + 1)).floor().long().minimum(h - ch)      # randint(0, h - ch + 1)
+    left = (u[3].gather(1, first)[:, 0] * (w - cw + 1)).floor().long().minimum(w - cw)
+    in_ratio = w / h
+    if in_ratio < ratio[0]:
+        fw, fh = w, int(round(w / ratio[0]))          # w / h < ratio[0]: below h
+    elif in_ratio > ratio[1]:
+        fh, fw = h, int(round(h * ratio[1]))          # w / h > ratio[1]: below w
+    else:
+        fw, fh = w, h
+    ch, cw = torch.where(found, ch, fh), torch.where(found, cw, fw)
+    top, left = torch.where(found, top, (h - fh) // 2), torch.where(found, left, (w - fw) // 2)
+    flip = (torch.rand(n, generator=generator, dtype=torch.float64) < p_flip).long()
+    return torch.stack((top, left, ch, cw, flip), dim=1).to(torch.int32)
+
+
+def _check_crops(crops, n, h, w, who):
+    """the (n, 5) descriptor tensor on the host, validated before anything is launched -> (crops int32 contiguous, max ch, max cw)"""
+    if not isinstance(crops, torch.Tensor) or crops.is_cuda or crops.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{who}: crops: an integer CPU tensor (n, 5) of (top, left, ch, cw, flip) expected")
+    if tuple(crops.shape) != (n, 5):
+        raise ValueError(f"{who}: crops of shape {tuple(crops.shape)} for {n} frames: ({n}, 5) expected")
+    c = crops.to(torch.int64)
+    top, left, ch, cw, flip = c.unbind(1)
+    if n and not bool(((ch >= 1) & (cw >= 1) & (top >= 0) & (left >= 0) & (top + ch <= h) & (left + cw <= w)).all()):
+        raise ValueError(f"{who}: a crop box is empty or leaves the {h} x {w} frame")
+    if n and not bool(((flip == 0) | (flip == 1)).all()):
+        raise ValueError(f"{who}: flip must be 0 or 1")
+    return c.to(torch.int32).contiguous(), (int(ch.max()) if n else 1), (int(cw.max()) if n else 1)
+
+
+def resized_crop_u8_reference(frames, crops, n_px=224):
+    """torchvision's resized_crop(frame, top, left, ch, cw, (n_px, n_px), BICUBIC) + the horizontal flip on a PIL image, restated as
+    Pillow's integer arithmetic: frames (n, h, w, 3) uint8 (numpy array or CPU tensor), crops (n, 5) of (top, left, ch, cw, flip)
+    -> (n, n_px, n_px, 3) uint8 of the same kind.  The crop is cut out first (the taps clip at ITS edge), its columns are resampled
+    with the table of (cw -> n_px) and rounded to uint8, then its rows with the table of (ch -> n_px); an axis of n_px pixels is
+    not resampled; a flipped frame has its output columns reversed.  Host-side mirror of dvla_image_resized_crop
+    (csrc/image_resized_crop.hip); tests pin it against Pillow byte for byte."""
+    is_tensor = isinstance(frames, torch.Tensor)
+    a = frames.numpy() if is_tensor else np.asarray(frames)
+    if a.dtype != np.uint8 or a.ndim != 4 or a.shape[-1] != 3:
+        raise TypeError("resized_crop_u8_reference: uint8 frames (n, h, w, 3) expected")
+    n, h, w = a.shape[:3]
+    boxes, _, _ = _check_crops(torch.as_tensor(np.asarray(crops)), n, h, w, "resized_crop_u8_reference")
+    out = np.empty((n, n_px, n_px, 3), np.uint8)
+    for i, (top, left, ch, cw, flip) in enumerate(boxes.tolist()):
+        crop = a[i, top:top + ch, left:left + cw]
+        mid = _resample_axis(crop, 1, *_axis_tables(cw, n_px), 0, n_px)
+        res = _resample_axis(mid, 0, *_axis_tables(ch, n_px), 0, n_px)
+        out[i] = res[:, ::-1] if flip else res
+    return torch.from_numpy(out) if is_tensor else out
+
+
+_crop_table_stores = {}
+
+
+def _pack_crop_tables(max_size, n_px):
+    """the tables of every input size 1 .. max_size for the output size n_px in one int32 array, as csrc/image_resized_crop.hip reads
+    it: a directory of (offset, ksize) per size (size 0 unused) and behind it, at each even offset, bounds (n_px, 2) then
+    coefficients (n_px, ksize)"""
+    head = 2 * (max_size + 1)
+    parts, directory, off = [], np.zeros((max_size + 1, 2), np.int32), head
+    for s in range(1, max_size + 1):
+        bounds, kk = _axis_tables(s, n_px)
+        directory[s] = (off, kk.shape[1])
+        parts += [bounds.reshape(-1), kk.reshape(-1)]
+        off += bounds.size + kk.size
+        if off % 2:                                   # bounds are read as 8-byte (first, count) pairs
+            parts.append(np.zeros(1, np.int32))
+            off += 1
+    return np.concatenate([directory.reshape(-1)] + parts).astype(np.int32)
+
+
+def _crop_table_store(device, h, w, n_px):
+    """the device-resident table store of one (device, input size, n_px): built and uploaded on first use (every size up to
+    max(h, w): about 2 ms of Python per size), then only looked up -> (int32 device tensor, max_size)"""
+    key = (device, h, w, n_px)
+    if key not in _crop_table_stores:
+        max_size = max(h, w)
+        _crop_table_stores[key] = (torch.from_numpy(_pack_crop_tables(max_size, n_px)).to(device), max_size)
+    return _crop_table_stores[key]
+
+
+def _resized_crop(frames_u8, crops, n_px, kind, mean, std, who):
+    import ctypes as C
+    from . import _lib
+    from .ops import _stream
+    lib = _lib.load()
+    if not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8:
+        raise TypeError(f"{who}: uint8 tensor (..., h, w, 3) expected")
+    if frames_u8.dim() < 3 or frames_u8.shape[-1] != 3:
+        raise ValueError(f"{who}: channels-last RGB frames expected")
+    lead, (h, w) = frames_u8.shape[:-3], frames_u8.shape[-3:-1]
+    n_px = int(n_px)
+    if h < 1 or w < 1 or n_px < 1:
+        raise ValueError(f"{who}: empty frames")
+    if kind == _lib.CROP_OUT_BF16 and n_px % 8:
+        raise ValueError(f"{who}: n_px = {n_px}: the bf16 kind stores 8 pixels at a time (n_px % 8 == 0), as preprocess_frames does")
+    n = math.prod(lead)
+    boxes, max_ch, max_cw = _check_crops(crops, n, h, w, who)
+    if not frames_u8.is_cuda:
+        raise _lib.DvlaError(f"{who}: tensor is on {frames_u8.device}; the HIP input pipeline has no CPU fallback")
+    src =frames_u8.reshape(-1, h, w, 3).contiguous()
+    if kind == _lib.CROP_OUT_BF16:
+        out = torch.empty((n, 3, n_px, n_px), dtype=torch.bfloat16, device=src.device)
+        m3, s3 = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    else:
+        out = torch.empty((n, n_px, n_px, 3), dtype=torch.uint8, device=src.device)
+        m3 = s3 = None
+    if n:
+        store, max_size = _crop_table_store(src.device, h, w, n_px)
+        dev_boxes = boxes.pin_memory().to(src.device, non_blocking=True)   # the call's one host -> device copy; the host does not wait
+        _lib.check(lib.dvla_image_resized_crop(src.data_ptr(), out.data_ptr(), dev_boxes.data_ptr(), store.data_ptr(), n, h, w, max_size,
+                                               max_ch, max_cw, n_px, kind, m3, s3, _stream()), "dvla_image_resized_crop")
+    return out.view(*lead, *out.shape[1:])
+
+
+def resized_crop_u8(frames_u8, crops, n_px=224):
+    """frames_u8: (..., h, w, 3) uint8 CUDA tensor (raw frames of one size); crops: (n, 5) integer CPU tensor of (top, left, ch, cw,
+    flip), one row per frame (`draw_resized_crops`) -> (..., n_px, n_px, 3) uint8 on the device: every frame cropped to its own
+    box, resized to n_px x n_px (BICUBIC) and flipped where flip = 1, bit-identical to Pillow's crop -> resize -> transpose
+    (`resized_crop_u8_reference`), one HIP kernel (no CPU fallback).  The boxes are validated on the host before the launch."""
+    from . import _lib
+    return _resized_crop(frames_u8, crops, n_px, _lib.CROP_OUT_U8, None, None, "resized_crop_u8")
+
+
+def resized_crop(frames_u8, crops, n_px=224, mean=CLIP_MEAN, std=CLIP_STD):
+    """`resized_crop_u8` with ToTensor + Normalize + the bf16 cast fused in -> (..., 3, n_px, n_px) bf16 on the device,
+    bit-identical to `preprocess_frames(resized_crop_u8(frames_u8, crops, n_px), mean=mean, std=std)`; n_px % 8 == 0."""
+    from . import _lib
+    return _resized_crop(frames_u8, crops, n_px, _lib.CROP_OUT_BF16, mean, std, "resized_crop")
 
 
 def draw_shifts(n, pad, traj=False, generator=None):

@@ -22,6 +22,7 @@ import torch
 from torch import nn
 
 from . import ops
+from . import preprocess as P
 from .nn import Block, LayerNorm, Linear, PatchEmbed
 
 
@@ -183,3 +184,30 @@ class MaskedAutoencoderViT(nn.Module):
         mask = torch.zeros(n, L, device=x.device)
         ids_restore = torch.arange(L, device=x.device).unsqueeze(0).expand(n, -1)
         return x, mask, ids_restore
+
+
+class MAEFrameAugment:
+    """The input side of MAE pretraining on the device: RandomResizedCrop(n_px, scale, ratio, BICUBIC) + RandomHorizontalFlip +
+    ToTensor + Normalize of the MAE recipe, from raw uint8 frames to the `imgs` of `MaskedAutoencoderViT.forward`:
+
+        augment = MAEFrameAugment()
+        loss, pred, mask = mae(augment(frames_u8), mask_ratio=0.75)       # frames_u8 (n, h, w, 3) uint8 on the device
+
+    One call = one draw of the boxes on the host (`preprocess.draw_resized_crops`, the algorithm of torchvision's get_params on
+    this package's own random stream: DESIGN.md section 5), one upload of the (n, 5) descriptors and one launch of
+    csrc/image_resized_crop.hip, whose bytes are Pillow's.  mean / std default to CLIP's: that is what DreamVLA's encoder, which
+    the pretrained weights are loaded into (`vit_checkpoint_path`), is fed by `preprocess_frames`.  `last_crops` keeps the
+    descriptors of the latest call."""
+
+    def __init__(self, n_px=224, scale=(0.2, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), p_flip=0.5, mean=P.CLIP_MEAN, std=P.CLIP_STD, generator=None):
+        self.n_px, self.scale, self.ratio, self.p_flip = int(n_px), tuple(scale), tuple(ratio), float(p_flip)
+        self.mean, self.std = tuple(mean), tuple(std)
+        self.generator = generator
+        self.last_crops = None
+
+    def __call__(self, frames_u8):
+        if not isinstance(frames_u8, torch.Tensor) or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
+            raise ValueError("MAEFrameAugment: frames (n, h, w, 3) expected")
+        n, h, w = frames_u8.shape[:3]
+        self.last_crops = P.draw_resized_crops(n, h, w, self.scale, self.ratio, self.p_flip, generator=self.generator)
+        return P.resized_crop(frames_u8, self.last_crops, self.n_px, self.mean, self.std)

@@ -435,6 +435,29 @@ int dvla_image_preprocess(const uint8_t* src, const int32_t* shift, void* out, i
 int dvla_image_resize_u8(const uint8_t* src, uint8_t* out, int64_t n, int32_t src_h, int32_t src_w, int32_t res_h, int32_t res_w,
                          const int32_t* bounds_x, const int32_t* coef_x, int32_t ksize_x, const int32_t* bounds_y,
                          const int32_t* coef_y, int32_t ksize_y, int32_t crop_left, int32_t crop_top, int32_t n_px, void* stream);
+/* (additive, ABI 8) MAE pretraining from raw frames: torchvision's resized_crop(frame, top, left, ch, cw, (n_px, n_px),
+ * BICUBIC) followed by an optional horizontal flip, with ONE BOX PER FRAME, byte for byte what Pillow's crop -> resize -> transpose
+ * gives: the arithmetic of dvla_image_resize_u8 on the tables of the size pairs (cw -> n_px) horizontally and (ch -> n_px) vertically,
+ * the taps clipped at the crop's edge.  src: (n, src_h, src_w, 3) uint8, contiguous, any alignment.
+ * crops: (n, 5) int32 on the device = (top, left, ch, cw, flip) per frame; flip != 0 writes output column x to n_px - 1 - x.
+ * table_store: int32 on the device, 8-byte aligned, built by the CALLER (dreamvla_amd/preprocess.py: _crop_table_store) for every input
+ * size s = 0 .. max_size:  store[2 s] = offset (even, in int32 words from the base) of size s's tables, store[2 s + 1] = their ksize;
+ * at the offset bounds (n_px, 2) = (first input index, tap count <= ksize) and behind them coefficients (n_px, ksize) at 22 fractional
+ * bits (the identity table -- bounds (i, 1), coefficient 2^22, ksize 1 -- for s == n_px; size 0 is never read).
+ * max_ch, max_cw: the largest ch and cw among the n descriptors (the host knows them: it drew the boxes); the launch's LDS plan is
+ * made for them.  A frame whose box leaves the source, has ch or cw < 1, or exceeds max_ch / max_cw rows / columns WRITES NOTHING.
+ * out_kind DVLA_CROP_OUT_U8: out (n, n_px, n_px, 3) uint8 at any address; mean3 / std3 unused (may be NULL).
+ * out_kind DVLA_CROP_OUT_BF16: out (n, 3, n_px, n_px) bf16 = dvla_image_preprocess (no shift) of the uint8 kind, bit for bit: fp32
+ * byte / 255, - mean3[c], / std3[c], one rounding to bf16; n_px % 8 == 0 and out 16-byte aligned, else DVLA_ERR_UNSUPPORTED.
+ * n == 0: DVLA_OK.  DVLA_ERR_ARG: a null pointer, a size < 1, max_ch > min(src_h, max_size), max_cw > min(src_w, max_size), another
+ * out_kind.  DVLA_ERR_UNSUPPORTED: the LDS plan of ONE output row -- min(max_ch, ksize(max_ch)) rows of align16(3 n_px) bytes plus
+ * four staging buffers of 3 max_cw + 31 bytes -- exceeds 64 KiB, src_h or src_w > 2^20, n_px > 2^14, a misaligned table_store or
+ * crops, or more than 2^31 - 1 workgroups. */
+#define DVLA_CROP_OUT_U8 0
+#define DVLA_CROP_OUT_BF16 1
+int dvla_image_resized_crop(const uint8_t* src, void* out, const int32_t* crops, const int32_t* table_store, int64_t n, int32_t src_h,
+                            int32_t src_w, int32_t max_size, int32_t max_ch, int32_t max_cw, int32_t n_px, int32_t out_kind,
+                            const float* mean3, const float* std3, void* stream);
 /* (additive, ABI 8) Depth labels on the device: raw fp32 depth maps -> the collator's nearest resize
  * (`depth_image_fn`, utils/data_utils.py:3588-3607 = F.interpolate(mode="nearest")) -> RandomShiftsAug as the integer-shift gather
  * -> cast, one launch:
