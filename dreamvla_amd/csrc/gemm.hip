@@ -299,6 +299,16 @@ bool ring_ok(const GemmKArgs& a, int combo) {
   const int64_t a_far = (int64_t)(((combo & 2) ? RC::BKS : RC::BM) - 1) * a.lda * 2 + 2 * (int64_t)((combo & 2) ? RC::BM : RC::BKS);
   const int64_t b_far = (int64_t)(((combo & 1) ? RC::BKS : RC::BN) - 1) * a.ldb * 2 + 2 * (int64_t)((combo & 1) ? RC::BN : RC::BKS);
   if (a_far >= (1ll << 32) || b_far >= (1ll << 32)) return false;
+  // the same on the output side: the whole-line epilogue (gemm_impl.h RowWindow) addresses C, the pre-activation, the act' operand
+  // and a non-periodic residual as a 32-bit byte offset from element (first row of the wave's window, its first column).  The
+  // far corner of the tallest window -- row EPI_WINDOW_ROWS - 1, the last 16 bytes of its 64-column line -- must stay below
+  // 4 GiB; one bound for every configuration and epilogue class (the 64-row windows and the classes that address in 64 bits
+  // could go further, but the contract in dvla.h is one number).  A periodic residual keeps the flat 64-bit form.
+  auto window_far = [](int64_t ld, int elem) { return (int64_t)(EPI_WINDOW_ROWS - 1) * ld * elem + 64 * (int64_t)elem; };
+  if (window_far(a.ldc, a.c_f32 ? 4 : 2) >= (1ll << 32)) return false;
+  if (a.preact && window_far(a.ld_preact, 2) >= (1ll << 32)) return false;
+  if (a.dact_aux && window_far(a.ld_dact, 2) >= (1ll << 32)) return false;
+  if (a.residual && a.res_rows <= 0 && window_far(a.ld_res, 2) >= (1ll << 32)) return false;
   return true;
 }
 

@@ -916,8 +916,13 @@ __device__ __forceinline__ void quad_transpose(u32x4 (&P)[4], int /*lane*/) {
 //     cost ~9 VALU instructions of 64-bit address arithmetic + a compare / saveexec / branch per 16-byte store, a third of the
 //     VALU work of a plain slab, in an epilogue that is VALU-bound with the matrix pipe idle (profiles/r05_gemm_boundary.txt);
 //   * rows at or past M fall outside the descriptor: stores are dropped, loads return zero -- no row test, no clamp.
-// (offsets inside a wave's 128 rows x 64 columns stay below 4 GiB for any leading dimension the dispatcher admits; the size field
-// saturates at 4 GiB - 1, which can only happen when all 128 rows are inside the matrix anyway.)
+// The largest offset is that of the window's far corner: row EPI_WINDOW_ROWS - 1 (4 qa + 32 j + c <= 127), the last 16 bytes of the
+// 64-column line.  The dispatcher (gemm.hip ring_ok, and through it phase_ok) admits a problem to these kernels only if
+//   (EPI_WINDOW_ROWS - 1) * ld * ELEM + 64 * ELEM < 2^32
+// holds for C, the pre-activation, the act' operand and a non-periodic residual -- ld up to ~16.9 M bf16 elements; anything wider
+// goes to the register-staged kernel, whose epilogue_oct addresses in 64 bits.  The size field saturates at 4 GiB - 1, which under
+// that bound can only happen when all rows of the window are inside the matrix anyway.
+constexpr int EPI_WINDOW_ROWS = 128;    // the tallest wave window of any configuration (TM = 4 slabs of 32 rows)
 struct RowWindow {
   __amdgpu_buffer_rsrc_t rs;
   uint32_t lane_off;      // this lane's byte offset: row 4 qa of the window, its 16 bytes of the line
@@ -948,6 +953,7 @@ template <int TM, int EPI, class ST = NoStamp, bool NO_BIAS = false>
 __device__ __forceinline__ void reg_epilogue(const GemmKArgs& p, f32x16 (&acc)[2][TM], int lane, int64_t m_base,
                                              int64_t n_base, int split, ST st = ST()) {
   if (n_base >= p.N) return;   // N % 64 == 0: a wave's 64 columns are all inside or all outside
+  static_assert(TM * 32 <= EPI_WINDOW_ROWS, "the dispatcher's stride bound is written for windows of at most EPI_WINDOW_ROWS rows");
   constexpr bool AUXV = epi_aux(EPI);            // store-layout operand vectors are prefetched (bf16 outputs)
   constexpr bool AUX = AUXV || EPI == EPI_F32;   // the class may read an act' operand / a residual / old C values at all
   const int l31 = lane & 31, g = lane >> 5;

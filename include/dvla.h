@@ -55,7 +55,27 @@ int dvla_abi_version(void);
  *   models/perceiver_resampler.py:11-18,49-51,61, models/dreamvla_model.py:652-664,718-724,800-809,
  *   models/action_model/models.py:34-41,128-141,158-160, and their autograd backward GEMMs.
  * split_k > 1: K is cut in split_k slices written to `workspace` (split_k*M*N fp32) and reduced by a
- *   second kernel; only valid with the plain epilogue (used for weight gradients).
+ *   second kernel.  Plain epilogue, fp32 C and `accumulate` (the weight gradients), or bias / activation / residual applied by
+ *   the reduction pass (forward GEMMs with few hundred rows and a long K); never with preact, dact_aux or dropout
+ *   (DVLA_ERR_ARG).
+ *
+ * Addressing.  Every matrix has its own leading dimension (lda, ldb, ldc, ld_preact, ld_dact, ld_res, in elements) and may be a
+ *   view into a wider buffer; the library writes the M x N windows of C and preact and nothing else.  residual with
+ *   res_rows > 0 is a table of res_rows rows, row m % res_rows added to output row m.  bias is bf16 or fp32 (bias_dtype).
+ *   * Vector paths (16-byte accesses) need, per matrix: a 16-byte aligned base and a leading dimension that is a multiple of
+ *     8 elements (fp32 C: of 4); for the bias: a 16-byte aligned base.  Ragged sizes are fine for configuration 2 and 11; the
+ *     ring / phase configurations (4, 6, 7, 8, 9, 10) additionally need N % 64 == 0 and whole K-tiles.
+ *   * A call in which any of A, B, C, preact, dact_aux, residual or bias misses that is not taken by configurations 4 - 10:
+ *     it runs on configuration 2 (register-staged kernel, element-wise guarded epilogue) whatever was forced, with the same
+ *     values.  Configuration 11 needs A and B vectorisable only; a misaligned C / preact / dact_aux / residual / bias selects
+ *     its element-wise epilogue.
+ *   * An explicit split_k > 1 with bias / activation / residual needs N % 8 == 0 and vectorisable C, bias and residual:
+ *     DVLA_ERR_UNSUPPORTED before any launch otherwise.
+ *   * Stride bounds of configurations 4 - 10 (32-bit byte offsets inside a tile; wider views run on configuration 2, which
+ *     addresses in 64 bits): for a k-contiguous operand (tile rows - 1) * ld * 2 + 2 * K-tile < 2^32, for an r-contiguous one
+ *     (K-tile - 1) * ld * 2 + 2 * tile rows < 2^32; the phase kernel (8, 9, 10) also needs rows * ld * 2 < 2^32 for the whole
+ *     of A and of B; and for C, preact, dact_aux and a residual with res_rows == 0: 127 * ld * element size + 64 * element
+ *     size < 2^32, i.e. ld below about 16.9 M bf16 elements.
  */
 typedef struct dvla_gemm_params {
   const void* A; int64_t lda; int32_t a_trans;

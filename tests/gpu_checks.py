@@ -149,6 +149,269 @@ def check_gemm_wide_stride(variant=7, M=300, N=256, K=128, stride=8_500_000):
     return out
 
 
+# the whole-line epilogue of the ring / phase kernels addresses a wave's window of at most 128 rows (csrc/gemm_impl.h
+# EPI_WINDOW_ROWS) with 32-bit byte offsets: the smallest bf16 row stride, in whole 16-byte vectors, at which the window's last
+# row lies >= 4 GiB behind its first -- (128 - 1) * stride * 2 >= 2^32 -> 16 909 328 elements
+WINDOW_ROWS = 128
+WIDE_OUT_STRIDE = (-(-(1 << 32) // (2 * (WINDOW_ROWS - 1))) + 7) // 8 * 8
+
+
+def check_gemm_wide_stride_out(variant=4, which="out", M=256, N=256, K=128):
+    """the output side of check_gemm_wide_stride: `out=` (which = "out") or `residual` (which = "residual") is a view whose row stride
+    is WIDE_OUT_STRIDE = 16 909 328 elements, the smallest multiple of 8 at which row 127 of a wave's 128-row window lies >= 4 GiB
+    behind row 0 (127 x 16 909 328 x 2 B = 2^32 + 2016).  The ring / phase kernels' RowWindow (32-bit byte offsets) cannot reach
+    that row; the dispatcher's bound (csrc/gemm.hip ring_ok, one bound for every configuration: the tallest window) has to hand the
+    problem to the register-staged kernel, which addresses in 64 bits -- the kernel the operand-side case already runs at such
+    strides.  Right values, every element of the M x N window written, `dvla_last_gemm_variant() == 2`.  The backing buffer covers
+    all M rows in full (M x stride elements, 8.66 GB) and is freed before the case returns."""
+    from dreamvla_amd import ops
+    from dreamvla_amd._lib import load
+    stride = WIDE_OUT_STRIDE
+    g = torch.Generator().manual_seed(78)
+    A = rnd((M, K), g)
+    B = rnd((N, K), g, 1.0 / math.sqrt(K))
+    res = rnd((M, N), g)
+    ref = A.double() @ B.double().t()
+    big = torch.empty(M * stride, device=DEV, dtype=BF)
+    view = torch.as_strided(big, (M, N), (stride, 1))
+    with torch.no_grad():
+        if which == "out":
+            view.fill_(float("nan"))          # an element the kernel does not write stays non-finite
+            got = ops.gemm(A.to(DEV, BF), B.to(DEV, BF), out=view, variant=variant)
+        else:
+            view.copy_(res.to(DEV, BF))
+            got = ops.gemm(A.to(DEV, BF), B.to(DEV, BF), residual=view, variant=variant)
+            ref = R.bf16_round(ref).double() + res.double()
+    ran = int(load().dvla_last_gemm_variant())
+    got = got.float().cpu()
+    tag = f"gemm v{variant} forced, {which} a view with a row stride of {stride} elements"
+    out = [metrics(tag, got, ref, TOL_FWD),
+           {"name": tag + ": window fully written", "rel_l2": 0.0, "tol": 0.0, "ok": bool(torch.isfinite(got).all())},
+           {"name": tag + f": ran the register-staged kernel (last variant {ran})", "rel_l2": 0.0, "tol": 0.0, "ok": ran == 2}]
+    del big, view
+    torch.cuda.empty_cache()
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# GEMM addressing: operands, outputs and epilogue operands as VIEWS into wider buffers (own leading dimension and origin each),
+# the periodic residual, the fp32 bias.  tests/test_gemm_addressing_gpu.py holds the case matrix, tests/test_gemm_views.py checks
+# the helpers themselves on the CPU.
+# ---------------------------------------------------------------------------------------------------
+VIEW_SENTINEL = -6.625      # finite, exact in bf16 and fp32; the backing buffers are filled with it before a call
+ERR_UNSUPPORTED = -3        # csrc/common.h DVLA_ERR_UNSUPPORTED
+
+
+def make_view(rows, cols, pad=0, offset=0, dtype=BF, device="cpu", lead_rows=2, trail_rows=2, sentinel=VIEW_SENTINEL):
+    """-> (backing, view): a rows x cols window with leading dimension cols + pad inside a 1-D buffer filled with `sentinel`.  The
+    window's origin lies `offset` elements behind a 128-byte boundary that has at least `lead_rows` rows of the buffer in front of
+    it; `trail_rows` rows follow the last one.  (offset % 8 == 0 and pad % 8 == 0 -- fp32: % 4 -- give what the vector paths need.)"""
+    ld = cols + pad
+    origin = -(-(lead_rows * ld) // 64) * 64 + offset
+    backing = torch.full((origin + (rows + trail_rows) * ld,), sentinel, dtype=dtype, device=device)
+    return backing, torch.as_strided(backing, (rows, cols), (ld, 1), origin)
+
+
+def _bits(t):
+    return t.view(torch.int16 if t.element_size() == 2 else torch.int32)
+
+
+def window_mask(backing, view):
+    """bool per element of `backing`: inside the rows x cols window `view` covers"""
+    origin = view.storage_offset() - backing.storage_offset()
+    rows, cols = view.shape
+    ld = max(int(view.stride(0)), 1)
+    idx = torch.arange(backing.numel(), device=backing.device) - origin
+    return (idx >= 0) & (idx < (rows - 1) * ld + cols) & (idx % ld < cols)
+
+
+def outside_window_intact(backing, view, sentinel=VIEW_SENTINEL):
+    """every element of `backing` outside the window of `view` (padding columns, rows before / after, the elements left and right
+    of an offset origin) is bit-identical to the sentinel; view = None: the whole buffer"""
+    want = int(_bits(torch.tensor([sentinel], dtype=backing.dtype))[0])
+    bad = _bits(backing) != want
+    if view is not None:
+        bad &= ~window_mask(backing, view)
+    n = int(bad.sum())
+    return {"ok": n == 0, "bad": n, "first_bad": int(bad.nonzero()[0]) if n else -1}
+
+
+_VIEW_DATA = {}
+
+
+def _view_case_data(M, N, K, seed=0):
+    """seeded operands of a view case + their float64 product, computed once per shape and shared (never modified)"""
+    key = (M, N, K, seed)
+    if key not in _VIEW_DATA:
+        if len(_VIEW_DATA) >= 8:
+            _VIEW_DATA.clear()
+        g = torch.Generator().manual_seed(9000 + seed)
+        d = {"A": rnd((M, K), g), "B": rnd((N, K), g, 1.0 / math.sqrt(K)), "bias": rnd((N,), g), "res": rnd((M, N), g),
+             "aux": rnd((M, N), g), "c0": rnd((M, N), g)}
+        d["bias32"] = (d["bias"] * 1.0009765625).float()        # fp32 master values that are NOT bf16-representable
+        d["prod"] = d["A"].double() @ d["B"].double().t()
+        _VIEW_DATA[key] = d
+    return _VIEW_DATA[key]
+
+
+# (pad, origin offset) in elements of every view of an ALIGNED case: all different, all whole 16-byte vectors
+ALIGNED_VIEWS = {"a": (8, 8), "b": (16, 24), "out": (24, 16), "res": (40, 8), "aux": (8, 32), "bias": (0, 8), "preact": (56, 40)}
+
+
+def _gemm_call(lib, variant, a, b, out, M, N, K, a_trans, b_trans, bias, act, preact, aux, dact, dropout_p, seed, res, res_rows,
+               accumulate, split_k):
+    """dvla_gemm_bf16 through ctypes (every leading dimension as the tensors have it) -> (return code, what ran)"""
+    import ctypes as C
+    from dreamvla_amd import ops
+    from dreamvla_amd._lib import ACT, GemmParams
+    p = GemmParams()
+    p.A, p.lda, p.a_trans = a.data_ptr(), a.stride(0), int(a_trans)
+    p.B, p.ldb, p.b_trans = b.data_ptr(), b.stride(0), int(b_trans)
+    p.C, p.ldc, p.c_dtype = out.data_ptr(), out.stride(0), 1 if out.dtype == torch.float32 else 0
+    p.M, p.N, p.K = M, N, K
+    if bias is not None:
+        p.bias, p.bias_dtype = bias.data_ptr(), 1 if bias.dtype == torch.float32 else 0
+    p.act = ACT[act]
+    if preact is not None:
+        p.preact, p.ld_preact = preact.data_ptr(), preact.stride(0)
+    if aux is not None:
+        p.dact_aux, p.ld_dact, p.dact = aux.data_ptr(), aux.stride(0), ACT[dact]
+    p.dropout_p, p.seed_lo, p.seed_hi = float(dropout_p), seed[0], seed[1]
+    if res is not None:
+        p.residual, p.ld_res, p.res_rows = res.data_ptr(), res.stride(0), int(res_rows)
+    p.accumulate, p.split_k = int(accumulate), int(split_k)
+    ws = torch.empty((split_k, M, N), dtype=torch.float32, device=a.device) if split_k > 1 else None
+    if ws is not None:
+        p.workspace = ws.data_ptr()
+    lib.dvla_set_gemm_variant(int(variant or 0))
+    try:
+        rc = int(lib.dvla_gemm_bf16(C.byref(p), ops._stream()))
+    finally:
+        lib.dvla_set_gemm_variant(0)
+    torch.cuda.synchronize()          # (the workspace outlives the launches)
+    return rc, (int(lib.dvla_last_gemm_variant()) if rc == 0 else None)
+
+
+def check_gemm_views(M, N, K, a_trans=False, b_trans=False, bias=None, act="none", residual=False, res_rows=0, out_f32=False,
+                     accumulate=False, split_k=1, dropout_p=0.0, dact=None, want_preact=False, variant=None, expect=None,
+                     views=None, expect_rc=0, via_ops=False, seed=0):
+    """check_gemm with every tensor a view into a wider, sentinel-filled buffer: A, B, `out`, the pre-activation, the residual
+    (res_rows > 0: a table of that many rows, row m % res_rows added to output row m), the act' operand and the bias
+    ("bf16" / "f32").  `views` overrides (pad, origin offset) per tensor (ALIGNED_VIEWS otherwise).  The library is called through
+    ctypes (own ld_preact); via_ops: through ops.gemm(out=...) inside `with ops.forward_split_k()` instead.
+    Asserted: (1) the values against the float64 product of the bf16 operand values run through the epilogue oracle, tolerances
+    of check_gemm; (2) every element of the backing buffers of `out` / the pre-activation outside their M x N windows is
+    bit-identical to the sentinel, and no input buffer changed; (3) if a call on contiguous copies of the same data reports the
+    same dvla_last_gemm_variant(), its results are torch.equal (strides do not change summation order); (4) `expect`: the
+    configuration that ran.  expect_rc != 0: the call must return that code and write nothing at all."""
+    from dreamvla_amd import _lib, ops
+    from dreamvla_amd._lib import ACT
+    lib = _lib.load()
+    d = _view_case_data(M, N, K, seed)
+    vw = dict(ALIGNED_VIEWS, **(views or {}))
+    sd = (77, 4242)
+    odt = torch.float32 if out_f32 else BF
+
+    def view_of(name, src, dtype=BF):
+        src = src.view(1, -1) if src.dim() == 1 else src
+        backing, v = make_view(src.shape[0], src.shape[1], vw[name][0], vw[name][1], dtype, DEV)
+        v.copy_(src.to(DEV, dtype))
+        return backing, v
+
+    a_b, a_v = view_of("a", d["A"].t() if a_trans else d["A"])
+    b_b, b_v = view_of("b", d["B"].t() if b_trans else d["B"])
+    inputs = {"A": a_b, "B": b_b}
+    bias_v = res_v = aux_v = pre_b = pre_v = None
+    bias_val = None
+    if bias:
+        bias_val = d["bias32"] if bias == "f32" else d["bias"]
+        inputs["bias"], bias2 = view_of("bias", bias_val, torch.float32 if bias == "f32" else BF)
+        bias_v = bias2[0]
+    if residual:
+        inputs["residual"], res_v = view_of("res", d["res"][:res_rows] if res_rows > 0 else d["res"])
+    if dact:
+        inputs["dact_aux"], aux_v = view_of("aux", d["aux"])
+    out_b, out_v = make_view(M, N, vw["out"][0], vw["out"][1], odt, DEV)
+    if accumulate:
+        out_v.copy_(d["c0"].to(DEV, odt))
+    if want_preact:
+        pre_b, pre_v = make_view(M, N, vw["preact"][0], vw["preact"][1], BF, DEV)
+    before = {k: v.clone() for k, v in inputs.items()}
+    common = dict(M=M, N=N, K=K, a_trans=a_trans, b_trans=b_trans, act=act, dact=dact, dropout_p=dropout_p, seed=sd,
+                  res_rows=res_rows, accumulate=accumulate)
+    opts = [f"bias-{bias}" if bias else "", act if act != "none" else "", "preact" if want_preact else "", f"p{dropout_p}" if dropout_p else "",
+            f"dact-{dact}" if dact else "", ("res%" + str(res_rows) if res_rows else "res") if residual else "", "f32" if out_f32 else "",
+            "acc" if accumulate else "", f"sk{split_k}" if split_k > 1 else "", "via-ops" if via_ops else ""]
+    opts += [f"{k}:{v[0]}+{v[1]}" for k, v in sorted((views or {}).items())]
+    tag = (f"gemm views v{0 if variant is None else variant} {M}x{N}x{K} {'NT'[int(a_trans)]}{'NT'[int(b_trans)]} " + " ".join(o for o in opts if o)).rstrip()
+    out = []
+    if via_ops:       # the opportunistic forward split: must run UNSPLIT when the reduction pass cannot vectorise, and be right
+        would = ops.fwd_split_k(M, N, K) > 1 and not ops._fwd_split_epilogue_ok(out_v, bias_v, res_v, N)
+        out.append({"name": tag + ": a split the rule would take, refused for its epilogue operands", "rel_l2": 0.0, "tol": 0.0, "ok": bool(would)})
+        with ops.forward_split_k(), torch.no_grad():
+            ops.gemm(a_v, b_v, a_trans=a_trans, b_trans=b_trans, bias=bias_v, act=ACT[act], residual=res_v, res_rows=res_rows, out=out_v)
+        torch.cuda.synchronize()
+        rc, ran = 0, int(lib.dvla_last_gemm_variant())
+    else:
+        rc, ran = _gemm_call(lib, variant, a_v, b_v, out_v, bias=bias_v, preact=pre_v, aux=aux_v, res=res_v, split_k=split_k, **common)
+    if expect_rc != 0:
+        clean = outside_window_intact(out_b, None)
+        return [{"name": tag + f": return code {rc} (expected {expect_rc})", "rel_l2": 0.0, "tol": 0.0, "ok": rc == expect_rc},
+                {"name": tag + f": nothing written ({clean['bad']} elements changed)", "rel_l2": 0.0, "tol": 0.0, "ok": clean["ok"]}]
+    out.append({"name": tag + f": return code {rc}", "rel_l2": 0.0, "tol": 0.0, "ok": rc == 0})
+    if rc != 0:
+        return out
+    # (1) values
+    ref = d["prod"]
+    if bias:
+        ref = ref + bias_val.double()
+    pre_ref = ref
+    if want_preact:
+        ref = R.bf16_round(ref).double()
+    ref = R.act(ref, act)
+    if dropout_p > 0:
+        ref = R.dropout_elementwise(ref, dropout_p, sd)
+    if (dact or residual) and not out_f32:
+        ref = R.bf16_round(ref).double()
+    if dact:
+        x = d["aux"].double().requires_grad_(True)
+        R.act(x, dact).sum().backward()
+        ref = ref * x.grad
+    if residual:
+        ref = ref + (d["res"][torch.arange(M) % res_rows] if res_rows > 0 else d["res"]).double()
+    if accumulate:
+        ref = ref + d["c0"].double()
+    out.append(metrics(tag, out_v, ref, TOL_F32 if out_f32 else TOL_FWD, round_ref=not out_f32))
+    if want_preact:
+        out.append(metrics(tag + " preact", pre_v, pre_ref, TOL_FWD))
+    # (2) nothing outside the windows written, no input touched
+    for name, (bk, v) in {"out": (out_b, out_v), "preact": (pre_b, pre_v)}.items():
+        if bk is not None:
+            s = outside_window_intact(bk, v)
+            out.append({"name": tag + f": buffer around `{name}` intact ({s['bad']} elements changed, first at {s['first_bad']})",
+                        "rel_l2": float(s["bad"]), "tol": 0.0, "ok": s["ok"]})
+    changed = [k for k, v in inputs.items() if not torch.equal(_bits(v), _bits(before[k]))]
+    out.append({"name": tag + f": input buffers unchanged (changed: {changed})", "rel_l2": float(len(changed)), "tol": 0.0, "ok": not changed})
+    # (3) the same data contiguous: same configuration -> same bits (via_ops: the configuration that ran, forced and UNSPLIT -- a
+    # forward split that was taken after all would sum in another order)
+    cont = lambda t: None if t is None else torch.empty(t.shape, dtype=t.dtype, device=t.device).copy_(t)    # a fresh allocation
+    out_c = torch.empty((M, N), dtype=odt, device=DEV)
+    if accumulate:
+        out_c.copy_(d["c0"].to(DEV, odt))
+    pre_c = torch.empty((M, N), dtype=BF, device=DEV) if want_preact else None
+    rc_c, ran_c = _gemm_call(lib, ran if via_ops else variant, cont(a_v), cont(b_v), out_c, bias=cont(bias_v), preact=pre_c,
+                             aux=cont(aux_v), res=cont(res_v), split_k=1 if via_ops else split_k, **common)
+    same = rc_c == 0 and ran_c == ran
+    equal = (not same) or (torch.equal(out_v, out_c) and (pre_v is None or torch.equal(pre_v, pre_c)))
+    out.append({"name": tag + f": contiguous call ran {ran_c}, strided {ran}" + (": results bit-identical" if same else ": not compared"),
+                "rel_l2": 0.0, "tol": 0.0, "ok": bool(rc_c == 0 and equal), "compared": bool(same), "ran": ran})
+    # (4) what ran
+    if expect is not None:
+        out.append({"name": tag + f": configuration {expect} ran (dvla_last_gemm_variant = {ran})", "rel_l2": 0.0, "tol": 0.0,
+                    "ok": ran == expect, "ran": ran})
+    return out
+
+
 def check_gemm_skinny(forced=True, **kw):
     """the few-rows kernel (csrc/gemm_skinny.h: M <= 512, k-contiguous operands -- the shapes of a single-episode control step):
     the same oracle as every other configuration, plus the assertion that it is what ran (forced = variant 11; not forced = the
@@ -1172,6 +1435,11 @@ def all_checks(quick=False):
         (check_mlp_fn, dict(M=333, K=64, Hd=256, act="gelu_tanh", conv1d=True, dropout_p=0.1)),
         (check_misc, dict()),
     ]
+    # the output side of the wide-stride case (appended here: the ids of the cases above stay what they were).  One 8.66-GB
+    # buffer at a time, freed inside the case
+    for v in (4, 7, 8):
+        L += [(check_gemm_wide_stride_out, dict(variant=v, which="out")),
+              (check_gemm_wide_stride_out, dict(variant=v, which="residual"))]
     return L
 
 
