@@ -204,6 +204,10 @@ int dvla_layernorm_bwd_rows(const void* dy, const void* x, const void* gamma, in
  * holds key j (any order, every entry < 2^18): keys that no query can see are dropped from the key axis without
  * copying K/V, and the caller is free to ORDER the kept keys so that keys with the same audience share 32-key tiles
  * (dreamvla_amd.ops.build_mask_tables does); dk/dv rows that are not indexed are NOT written (the caller zero-fills them).
+ * Without key_index EVERY dk/dv row is written, the rows of keys that no query sees with zeros.
+ * ANY 0 / -inf pattern is a valid mask, Lq != Lk included (mask_bits_q has ceil(Lk/32) words per query, mask_bits_k ceil(Lq/32)
+ * per key).  A query that sees NO key gets o = 0 and lse = +inf; in the backward pass its dq is 0 and it contributes nothing to
+ * dk or dv, whatever its dout holds (tests/test_attention_masks_gpu.py holds the kernels to all of this).
  * lse (B*H*Lq fp32, natural-log-sum-exp of the scaled+masked scores) is written when non-NULL.
  * Replaces: F.scaled_dot_product_attention in timm Attention (vit_mae.py:202-203, dreamvla_model.py:806-904,
  * action_model/models.py:137), GPT2Attention._attn / GPT2SdpaAttention (models/gpt2.py:61-84,267-274),

@@ -1124,6 +1124,151 @@ def check_cross_attention(B, H, Lq, Lk, seed=0):
     return out
 
 
+def _exact(name, ok, **extra):
+    return dict({"name": name, "rel_l2": 0.0, "tol": 0.0, "ok": bool(ok)}, **extra)
+
+
+def check_attention_masked(case):
+    """HIP attention under an arbitrary 0 / -inf mask (a case of tests/attention_mask_cases.py) through ops.attn_fwd_raw /
+    ops.attn_bwd_raw: any (Lq, Lk), lse and pre-filled gradient buffers within reach.  q, k, v are strided views of one packed
+    buffer when Lq == Lk (what _SelfAttention passes), of a q and a kv buffer otherwise (_CrossAttention); dq, dk, dv are views of
+    buffers pre-filled with NaN.  Checked per case:
+      values    o, dq, dk, dv against oracle/torch_ref.py::attention_bf16, TOL_ATTN / TOL_ATTN_GRAD, both criteria of `metrics`
+      lse       finite rows against the oracle's (TOL_F32); rows of a query that sees no key are +inf exactly
+      blind     such a query's o and dq rows are == 0 (its dout is random data: a leak into dk / dv fails the value check)
+      writes    no NaN left in dq; with a key_index the dk / dv rows it names are NaN-free and every other row still holds the
+                pre-fill (the "NOT written" rule of include/dvla.h); without one every row is written, dead keys' rows == 0
+      period    batch row b carries the inputs of row b % period: every row of o, lse, dq, dk, dv equals its representative bit
+                for bit (several items per workgroup of the forward ring kernel); the oracle then sees `rows` sampled rows
+    -> (list of metric dicts, structure of the mask)"""
+    from dreamvla_amd import ops
+    from tests import attention_mask_cases as MC
+    B, H, Lq, Lk, D, p_drop = case["B"], case["H"], case["Lq"], case["Lk"], case["D"], case["dropout_p"]
+    vis, mask, mt = MC.tables(case, device=DEV)
+    struct = MC.structure(vis, mt)
+    scale = D ** -0.5
+    g = torch.Generator().manual_seed(4100 + 13 * D + case["seed"])
+    P = B if case["period"] is None else min(B, case["period"])
+    W = H * D
+    if Lq == Lk:
+        src = [rnd((P, Lq, 3 * W), g)]
+    else:
+        src = [rnd((P, Lq, W), g), rnd((P, Lk, 2 * W), g)]
+    do = rnd((P, Lq, W), g)
+    if P < B:
+        tile = lambda t: t.repeat(-(-B // P), 1, 1)[:B].contiguous()
+        src, do = [tile(t) for t in src], tile(do)
+    dev = [t.to(DEV, BF) for t in src]
+    grad = [torch.full_like(t, float("nan")) for t in dev]
+    if Lq == Lk:
+        v5, d5 = dev[0].view(B, Lq, 3, H, D), grad[0].view(B, Lq, 3, H, D)
+        (q, k, v), (dq, dk, dv) = v5.unbind(2), d5.unbind(2)
+        q_h, k_h, v_h = src[0].view(B, Lq, 3, H, D).unbind(2)
+    else:
+        kv5, dkv5 = dev[1].view(B, Lk, 2, H, D), grad[1].view(B, Lk, 2, H, D)
+        q, (k, v), dq, (dk, dv) = dev[0].view(B, Lq, H, D), kv5.unbind(2), grad[0].view(B, Lq, H, D), dkv5.unbind(2)
+        q_h, (k_h, v_h) = src[0].view(B, Lq, H, D), src[1].view(B, Lk, 2, H, D).unbind(2)
+    sd = (4711 + case["seed"], 1234567)
+    kw = dict(scale=scale, mask_tables=mt, dropout_p=p_drop, seed=sd, head_dim=D)
+    do_d = do.to(DEV, BF).view(B, Lq, H, D)
+    o, lse = ops.attn_fwd_raw(q, k, v, **kw)
+    ops.attn_bwd_raw(q, k, v, o, lse, do_d, dq, dk, dv, **kw)
+    torch.cuda.synchronize()
+
+    # oracle on the sampled batch rows, (B, H, L, D) layout
+    sel = _sample_rows(B, case["rows"])
+    idx = torch.tensor(sel)
+    heads = lambda t: t[idx].permute(0, 2, 1, 3)
+    key_index = None if mt is None or mt.key_index is None else mt.key_index.cpu().long()
+    drop_cols = None
+    if key_index is not None:
+        drop_cols = torch.zeros(Lk, dtype=torch.int64)
+        drop_cols[key_index] = torch.arange(mt.Lk)
+    ref_o, ref_lse, ref_dq, ref_dk, ref_dv = R.attention_bf16(
+        heads(q_h), heads(k_h), heads(v_h), scale=scale, mask=mask, drop=(p_drop, sd) if p_drop > 0 else None,
+        drop_cols=drop_cols, dout=heads(do.view(B, Lq, H, D)), batch_index=sel)
+    host = lambda t: t.detach().float().cpu()[idx].permute(0, 2, 1, 3)
+    got = {"o": host(o), "dq": host(dq), "dk": host(dk), "dv": host(dv)}
+    lse_h = lse.detach().cpu()[idx]
+    tag = "attn_masked " + case["id"]
+    named = torch.ones(Lk, dtype=torch.bool)
+    if key_index is not None:
+        named[:] = False
+        named[key_index] = True
+    blind = torch.zeros(Lq, dtype=torch.bool) if vis is None else torch.from_numpy(~vis.any(axis=1))
+    dead = torch.zeros(Lk, dtype=torch.bool) if vis is None else torch.from_numpy(~vis.any(axis=0))
+
+    # values (rows of dk / dv that the kernels do not write are compared where they ARE written: the named rows)
+    out = [metrics(tag + " o", got["o"], ref_o, TOL_ATTN), metrics(tag + " dq", got["dq"], ref_dq, TOL_ATTN_GRAD),
+           metrics(tag + " dk", got["dk"][:, :, named], ref_dk[:, :, named], TOL_ATTN_GRAD),
+           metrics(tag + " dv", got["dv"][:, :, named], ref_dv[:, :, named], TOL_ATTN_GRAD)]
+    # lse
+    fin = ~blind
+    if bool(fin.any()):
+        out.append(metrics(tag + " lse", lse_h[:, :, fin], ref_lse[:, :, fin], TOL_F32, round_ref=False))
+    pinf = lse_h[:, :, blind] == float("inf")
+    out.append(_exact(tag + f": lse of the {int(blind.sum())} blind queries is +inf", pinf.all()))
+    # blind queries
+    zero = lambda t: bool((t == 0).all())
+    out.append(_exact(tag + ": o and dq of blind queries are 0", zero(got["o"][:, :, blind]) and zero(got["dq"][:, :, blind])))
+    # coverage of writes, over the WHOLE batch
+    nan_rows = lambda t: torch.isnan(t.detach().float()).any(dim=-1).any(dim=2).any(dim=0).cpu()      # (B, L, H, D) -> per token row
+    all_nan = lambda t: torch.isnan(t.detach().float()).all(dim=-1).all(dim=2).all(dim=0).cpu()
+    out.append(_exact(tag + ": every dq row written", not bool(nan_rows(dq).any())))
+    for name, t in (("dk", dk), ("dv", dv)):
+        out.append(_exact(tag + f": every {name} row the tables name is written", not bool(nan_rows(t)[named].any())))
+        if key_index is not None:
+            out.append(_exact(tag + f": the {int((~named).sum())} {name} rows the tables do not name keep their pre-fill",
+                              all_nan(t)[~named].all()))
+        else:
+            out.append(_exact(tag + f": {name} of the {int(dead.sum())} dead keys is 0", zero(got[name][:, :, dead])))
+    finite = all(bool(torch.isfinite(t.detach().float()).all()) for t in (o, dq)) and \
+        all(bool(torch.isfinite(got[n][:, :, named]).all()) for n in ("dk", "dv"))
+    out.append(_exact(tag + ": everything written is finite", finite))
+    # every batch row equals its representative
+    if P < B and p_drop == 0.0:
+        same = all(torch.equal(_bits(t)[P:], _bits(t)[:B - P]) for t in (o, dq, dk, dv)) and torch.equal(lse[P:], lse[:B - P])
+        out.append(_exact(tag + f": all {B} batch rows == their representative (period {P})", same))
+    return out, struct
+
+
+def check_self_attention_uncompacted(case, runs=2):
+    """_SelfAttention.backward allocates its gradient with torch.empty_like and, under tables without a key_index (compact_keys =
+    False), zero-fills nothing: the dK/dV kernels must write every row themselves, dead keys' rows included.  ops.self_attention +
+    backward, `runs` times on freshly allocated inputs; before each backward a NaN-filled tensor of qkv's size is freed, so that
+    empty_like is likely to be handed poisoned memory.  qkv.grad must be finite and equal to the oracle's every time."""
+    from dreamvla_amd import ops
+    from tests import attention_mask_cases as MC
+    B, H, L, D = case["B"], case["H"], case["Lq"], case["D"]
+    vis, mask, mt = MC.tables(case, device=DEV)
+    g = torch.Generator().manual_seed(4200 + case["seed"])
+    qkv, do = rnd((B, L, 3 * H * D), g), rnd((B, L, H * D), g)
+    q, k, v = R.split_qkv(qkv, H)
+    res = R.attention_bf16(q, k, v, scale=D ** -0.5, mask=mask, dout=do.view(B, L, H, D).permute(0, 2, 1, 3))
+    want = torch.cat([R.merge_heads(t) for t in res[2:]], dim=-1)
+    dead = torch.from_numpy(~vis.any(axis=0))
+    W = H * D
+    tag = "self_attention " + case["id"]
+    out = [_exact(tag + ": tables carry neither a key_index nor a dead-key list", mt.key_index is None and not hasattr(mt, "dead_keys"))]
+    for run in range(runs):
+        qd = qkv.to(DEV, BF).requires_grad_(True)
+        o = ops.self_attention(qd, H, mask_tables=mt, head_dim=D)
+        poison = torch.full_like(qd, float("nan"))
+        del poison
+        probe = torch.empty_like(qd)          # (reported, not asserted: the caching allocator hands the freed block back)
+        poisoned = bool(torch.isnan(probe).all())
+        del probe
+        o.backward(do.to(DEV, BF))
+        got = qd.grad.detach().float().cpu()
+        out.append(metrics(tag + f" run {run} o", o, R.merge_heads(res[0]), TOL_ATTN))
+        out += [metrics(tag + f" run {run} {n}", got[..., i * W:(i + 1) * W], want[..., i * W:(i + 1) * W], TOL_ATTN_GRAD)
+                for i, n in enumerate(("dq", "dk", "dv"))]
+        out.append(_exact(tag + f" run {run}: dk / dv of the {int(dead.sum())} dead keys are 0", bool((got[:, dead, W:] == 0).all()),
+                          gradient_memory_was_nan=poisoned))
+        del qd, o
+    return out
+
+
 def check_linear_fn(M, K, N, act="none", conv1d=False, residual=False, bias=True, dropout_p=0.0, seed=0):
     from dreamvla_amd import ops
     from dreamvla_amd.ops import _Seeds
