@@ -496,7 +496,11 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, need_param_grads, dres2=None, grad_d
 
 
 def colsum(x2, out_dtype=torch.float32, out=None):
-    """column sums (bias gradients), written in out_dtype (fp32 or bf16) by the reduction kernel itself"""
+    """column sums (bias gradients), written in out_dtype (fp32 or bf16) by the reduction kernel itself.  x2 may be a view whose
+    rows lie stride(0) apart (any alignment); its columns must be adjacent -- the kernel takes ONE leading dimension, and no
+    caller has another layout to offer, so such a view is refused, not copied"""
+    if x2.dim() != 2 or (x2.shape[1] > 1 and x2.stride(1) != 1):
+        raise ValueError(f"colsum: a (rows, cols) operand with column stride 1, got shape {tuple(x2.shape)} stride {tuple(x2.stride())}")
     lib = _lib.load()
     rows, cols = x2.shape
     if out_dtype not in (torch.float32, BF16):

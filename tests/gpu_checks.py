@@ -1812,3 +1812,268 @@ def check_flat_adamw(seed=0):
     out.append({"name": "flat_adamw leaves never-used parameters untouched", "rel_l2": 0.0, "tol": 0.0,
                 "ok": bool(torch.equal(victim.detach(), before)) and not torch.equal(other.detach(), others_before)})
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# LayerNorm and element-wise kernels on the paths of tests/rowwise_cases.py, against the UNROUNDED float64 result
+# (tests/test_layernorm_paths_gpu.py, tests/test_elementwise_paths_gpu.py).
+#   LayerNorm y / dx, per row:   |got - ref64| <= ulp_bf16(ref64) / 2 + (1 + kappa_row) * 2^-20 * max_row |ref64|
+#     the final rounding, plus fp32 round-off (2^-24) amplified by the row's conditioning kappa = |mean| * rstd, with a factor 16
+#     for the accumulations.  A misplaced row or lane is off by about max_row |ref64|.
+#   activations, per element:    |got - ref64| <= ulp_bf16(ref64) / 2 + 2^-20 * |dy| * max(1, |x|)        (forward: dy = 1)
+#     8 fp32 ulps of 1: two 1-ulp hardware approximations (v_exp_f32, v_rcp_f32), doubled in tanh2, and the 1.5e-7 of the erfc form.
+# `slack` is the largest part of an error that the rounding term did not cover, relative to the row's (element's) scale, and
+# `allow_frac` the largest fraction of the allowance that was used: what DESIGN.md quotes.
+# ---------------------------------------------------------------------------------------------------
+LN_ALLOW = 2.0 ** -20
+ACT_ALLOW = 2.0 ** -20
+
+
+def ulp_bf16(ref64):
+    """spacing of bf16 at |ref64| (float64 tensor); subnormal spacing 2^-133 below 2^-126"""
+    _, e = torch.frexp(ref64.abs())
+    e = torch.where(ref64 == 0, torch.full_like(e, -1000), e)
+    return torch.ldexp(torch.ones_like(ref64), (e - 1).clamp(min=-126) - 7)
+
+
+def rowwise(name, got, ref64, kappa):
+    """the per-row LayerNorm criterion; ref64 (rows, cols) float64, kappa (rows,)"""
+    g = got.detach().double().cpu().reshape(ref64.shape)
+    finite = bool(torch.isfinite(g).all()) and bool(torch.isfinite(ref64).all())
+    d = (g - ref64).abs()
+    ex_row = (d - 0.5 * ulp_bf16(ref64)).clamp(min=0).amax(-1)
+    rowmax = ref64.abs().amax(-1)
+    allow = (1.0 + kappa.double()) * LN_ALLOW * rowmax
+    bad = ex_row > allow
+    nz = rowmax > 0
+    slack = float((ex_row[nz] / rowmax[nz]).max()) if bool(nz.any()) else 0.0
+    fr = torch.where(nz, ex_row / allow.clamp(min=1e-300), torch.zeros_like(ex_row))
+    frac = float(fr.max()) if fr.numel() else 0.0
+    idx = int(d.flatten().argmax()) if d.numel() else 0
+    return {"name": name, "rel_l2": rel_l2(g, ref64), "max_abs": float(d.max()) if d.numel() else 0.0, "worst_index": idx,
+            "slack": slack, "allow_frac": frac, "allow_frac_row": int(fr.argmax()) if fr.numel() else -1, "bad_rows": int(bad.sum()), "first_bad_row": int(bad.nonzero()[0]) if bool(bad.any()) else -1,
+            "finite": finite, "tol": LN_ALLOW, "shape": list(g.shape), "ok": bool(finite and not bad.any())}
+
+
+def elementwise(name, got, ref64, scale):
+    """the per-element activation criterion; scale = |dy| * max(1, |x|) (float64, broadcastable)"""
+    g = got.detach().double().cpu().reshape(ref64.shape)
+    finite = bool(torch.isfinite(g).all()) and bool(torch.isfinite(ref64).all())
+    d = (g - ref64).abs()
+    ex = (d - 0.5 * ulp_bf16(ref64)).clamp(min=0)
+    allow = ACT_ALLOW * scale.expand_as(ref64)
+    bad = ex > allow
+    nz = allow > 0
+    slack = float((ex[nz] / scale.expand_as(ref64)[nz]).max()) if bool(nz.any()) else 0.0
+    idx = int((ex - allow).flatten().argmax()) if d.numel() else 0
+    return {"name": name, "rel_l2": rel_l2(g, ref64), "max_abs": float(d.max()) if d.numel() else 0.0, "worst_index": idx,
+            "slack": slack, "allow_frac": slack / ACT_ALLOW, "bad": int(bad.sum()), "finite": finite, "tol": ACT_ALLOW,
+            "shape": list(g.shape), "ok": bool(finite and not bad.any())}
+
+
+def same_bits(name, got, want):
+    """bit for bit (NaN patterns: NaN where NaN is wanted)"""
+    got, want = got.detach().cpu(), want.detach().cpu()
+    ok = got.dtype == want.dtype and got.shape == want.shape
+    n = -1
+    if ok:
+        nan = torch.isnan(want) if want.is_floating_point() else torch.zeros(want.shape, dtype=torch.bool)
+        diff = torch.where(nan, ~torch.isnan(got), _bits(got) != _bits(want)) if want.is_floating_point() else got != want
+        n = int(diff.sum())
+    return {"name": name, "rel_l2": 0.0, "max_abs": 0.0, "tol": 0.0, "differing": n, "ok": bool(ok and n == 0)}
+
+
+def _dirty_pool(shape):
+    torch.full(tuple(shape), 7.0, device=DEV, dtype=BF)          # (dirty the allocator's pool: an unwritten gradient row would show)
+
+
+def _ln_ref64(x, w, b, eps, dy, dres=None):
+    """(y, dx, dgamma, dbeta) of R.layer_norm in float64 with autograd; dres: the fork's second path, loss += <x, dres>"""
+    xr = x.double().requires_grad_(True)
+    wr = w.double().requires_grad_(True) if w is not None else None
+    br = b.double().requires_grad_(True) if b is not None else None
+    yr = R.layer_norm(xr, wr, br, eps)
+    if dres is None:
+        yr.backward(dy.double())
+    else:
+        torch.autograd.backward([xr * 1.0, yr], [dres.double(), dy.double()])
+    dg = wr.grad if wr is not None else None
+    if dg is not None:
+        # rows of equal elements have x - mean = 0; the float64 oracle leaves ~1e-13 there, and where EVERY row is such a row that
+        # noise is all of dgamma.  Below 2^-36 sum_r |dy| (a real entry is ~sqrt(rows)) the reference is zero.
+        dg = torch.where(dg.abs() <= 2.0 ** -36 * dy.double().abs().sum(0), torch.zeros_like(dg), dg)
+    return yr.detach(), xr.grad, dg, (br.grad if br is not None else None)
+
+
+def _ln_run(kind, x, w, b, eps, dy, dres, pdt):
+    from dreamvla_amd import ops
+    xd = x.to(DEV, BF).requires_grad_(True)
+    wd = w.to(DEV, pdt).requires_grad_(True) if w is not None else None
+    bd = b.to(DEV, pdt).requires_grad_(True) if b is not None else None
+    _dirty_pool(x.shape)
+    if kind == "plain":
+        y = ops.layer_norm(xd, wd, bd, eps)
+        _dirty_pool(x.shape)
+        y.backward(dy.to(DEV, BF))
+    else:
+        r, y = ops.layer_norm_fork(xd, wd, bd, eps)
+        _dirty_pool(x.shape)
+        if dres is None:
+            y.backward(dy.to(DEV, BF))
+        else:
+            torch.autograd.backward([r, y], [dres.to(DEV, BF), dy.to(DEV, BF)])
+    return y.detach(), xd.grad, (wd.grad if wd is not None else None), (bd.grad if bd is not None else None)
+
+
+def ln_case_path(case):
+    from tests import rowwise_cases as RC
+    f, b = RC.ln_geometry(case["rows"], case["cols"]), RC.ln_geometry(case["rows"], case["cols"], backward=True)
+    return (f"fwd {f['blocks']} blocks x {f['trips']} trips (last {f['last_trip_rows']} rows), bwd {b['blocks']} x {b['trips']} "
+            f"(last {b['last_trip_rows']}), VPL {f['vpl']}, {f['last_slot_lanes']} lanes in the last slot")
+
+
+def check_layernorm_paths(case, seed=0):
+    """one row of tests.rowwise_cases.LN_CASES: ops.layer_norm / ops.layer_norm_fork against the float64 oracle, row by row"""
+    from dreamvla_amd import ops
+    from tests import rowwise_cases as RC
+    rows, cols, eps, kind = case["rows"], case["cols"], case["eps"], case["kind"]
+    x, _ = RC.make_rows(case["data"], rows, cols, 1000 + seed, eps)
+    w, b = RC.ln_params(cols, seed, case["affine"])
+    dy = RC.grad_like((rows, cols), seed)
+    dres = RC.grad_like((rows, cols), seed + 1) if kind == "fork" else None
+    pdt = torch.float32 if case["pf32"] else BF
+    kappa = RC.row_kappa(x, eps)[0]
+    y, dx, dg, db = _ln_run(kind, x, w, b, eps, dy, dres, pdt)
+    yr, dxr, dgr, dbr = _ln_ref64(x, w, b, eps, dy, dres)
+    tag = f"ln-paths {case['id']}"
+    out = [rowwise(tag + " y", y, yr, kappa), rowwise(tag + " dx", dx, dxr, kappa)]
+    if case["affine"]:
+        assert dg.dtype == pdt and db.dtype == pdt
+        out.append(metrics(tag + " dgamma", dg, dgr.float(), TOL_GRAD, round_ref=not case["pf32"]))
+        out.append(metrics(tag + " dbeta", db, dbr.float(), TOL_GRAD, round_ref=not case["pf32"]))
+    if case["data"] == "unit":          # the suite's two criteria on the suite's kind of data, at unchanged tolerances
+        out.append(metrics(tag + " y (rel-L2)", y, yr.float(), TOL_FWD))
+        out.append(metrics(tag + " dx (rel-L2)", dx, dxr.float(), TOL_GRAD))
+    if kind == "fork":                  # no residual gradient arrives: the plain LayerNorm's numbers, bit for bit
+        y1, dx1, dg1, db1 = _ln_run("fork", x, w, b, eps, dy, None, pdt)
+        y2, dx2, dg2, db2 = _ln_run("plain", x, w, b, eps, dy, None, pdt)
+        out += [same_bits(tag + " y == plain (dres None)", y1, y2), same_bits(tag + " dx == plain (dres None)", dx1, dx2)]
+        if case["affine"]:
+            out += [same_bits(tag + " dgamma == plain (dres None)", dg1, dg2), same_bits(tag + " dbeta == plain (dres None)", db1, db2)]
+    if case["stats"]:
+        xd = x.to(DEV, BF)
+        ys, mean, rstd = ops.layernorm_fwd(xd, w.to(DEV, pdt), b.to(DEV, pdt), eps, True)
+        _, m64, r64, _ = RC.row_kappa(x, eps)
+        q = cols * 2.0 ** -24 * x.double().abs().mean(-1)             # recursive summation: cols * u * mean |x_i|
+        dm = (mean.double().cpu() - m64).abs()
+        dr = (rstd.double().cpu() - r64).abs() / r64
+        allow_r = q * r64 + 2.0 ** -22                                 # q over the row's (regularised) std, plus rsqrtf
+        fin = bool(torch.isfinite(mean).all() and torch.isfinite(rstd).all())
+        out.append({"name": tag + " mean", "rel_l2": rel_l2(mean, m64), "max_abs": float(dm.max()), "allow_frac": float((dm / q).max()),
+                    "tol": 2.0 ** -24, "finite": fin, "ok": bool(fin and (dm <= q).all())})
+        out.append({"name": tag + " rstd", "rel_l2": rel_l2(rstd, r64), "max_abs": float(dr.max()), "allow_frac": float((dr / allow_r).max()),
+                    "tol": 2.0 ** -22, "finite": fin, "ok": bool(fin and (dr <= allow_r).all())})
+        out.append(same_bits(tag + " y of layernorm_fwd(want_stats) == y of layer_norm", ys, y))
+    return out
+
+
+def check_layernorm_last_tokens_paths(case, seed=0):
+    """one row of LAST_TOKENS_CASES: the row groups iterate (the zero-fill of the rows outside the groups on later trips); mixed rows"""
+    from dreamvla_amd import ops
+    from tests import rowwise_cases as RC
+    n, L, keep, cols, eps = case["n"], case["L"], case["keep"], case["cols"], 1e-5
+    x2, _ = RC.make_rows("mixed", n * L, cols, 2000 + seed, eps)
+    x = x2.view(n, L, cols)
+    w, b = RC.ln_params(cols, seed)
+    dy = RC.grad_like((n * keep, cols), seed)
+    kappa = RC.row_kappa(x2, eps)[0]
+    k_kept = kappa.view(n, L)[:, L - keep:].reshape(-1)
+
+    def run(two_step):
+        xd = x.to(DEV, BF).requires_grad_(True)
+        wd, bd = w.to(DEV, BF).requires_grad_(True), b.to(DEV, BF).requires_grad_(True)
+        _dirty_pool(x.shape)
+        y = ops.layer_norm(xd[:, L - keep:, :].reshape(-1, cols), wd, bd, eps) if two_step else ops.layer_norm_last_tokens(xd, wd, bd, eps, keep)
+        _dirty_pool(x.shape)
+        y.backward(dy.to(DEV, BF))
+        return y.detach(), xd.grad, wd.grad, bd.grad
+    y, dx, dg, db = run(False)
+    xr = x.double().requires_grad_(True)
+    wr, br = w.double().requires_grad_(True), b.double().requires_grad_(True)
+    yr = R.layer_norm(xr[:, L - keep:, :].reshape(-1, cols), wr, br, eps)
+    yr.backward(dy.double())
+    tag = f"ln-paths {case['id']}"
+    lead = dx[:, :L - keep, :]
+    out = [rowwise(tag + " y", y, yr.detach(), k_kept), rowwise(tag + " dx (whole buffer)", dx, xr.grad.view(n * L, cols), kappa),
+           {"name": tag + " leading tokens get exact zeros", "ok": bool((lead == 0).all()) if lead.numel() else True, "rel_l2": 0.0,
+            "max_abs": float(lead.float().abs().max()) if lead.numel() else 0.0, "tol": 0.0},
+           metrics(tag + " dgamma", dg, wr.grad.float(), TOL_GRAD), metrics(tag + " dbeta", db, br.grad.float(), TOL_GRAD)]
+    y2, dx2, dg2, db2 = run(True)
+    out += [same_bits(tag + " y == LayerNorm(copy of the slice)", y, y2), same_bits(tag + " dx == the two-step path", dx, dx2),
+            same_bits(tag + " dgamma == the two-step path", dg, dg2), same_bits(tag + " dbeta == the two-step path", db, db2)]
+    return out
+
+
+def check_layernorm_concat_paths(case, seed=0):
+    """one row of CONCAT_CASES: both launches with map_output, mixed rows, one side without input gradient"""
+    from dreamvla_amd import ops
+    from tests import rowwise_cases as RC
+    n, La, Lb, cols, eps, a_grad = case["n"], case["La"], case["Lb"], case["cols"], 1e-5, case["a_needs_grad"]
+    a2, _ = RC.make_rows("mixed", n * La, cols, 3000 + seed, eps)
+    b2, _ = RC.make_rows("mixed", n * Lb, cols, 3001 + seed, eps)
+    a, b = a2.view(n, La, cols), b2.view(n, Lb, cols)
+    (wa, ba), (wb, bb) = RC.ln_params(cols, seed), RC.ln_params(cols, seed + 1)
+    dy = RC.grad_like((n, La + Lb, cols), seed)
+    ka, kb = RC.row_kappa(a2, eps)[0], RC.row_kappa(b2, eps)[0]
+    k_all = torch.cat((ka.view(n, La), kb.view(n, Lb)), 1).reshape(-1)
+
+    def run(aten):
+        dev = lambda t, grad=True: t.to(DEV, BF).requires_grad_(grad)
+        ad, bd, p = dev(a, a_grad), dev(b), [dev(t) for t in (wa, ba, wb, bb)]
+        _dirty_pool(dy.shape)
+        if aten:
+            y = torch.cat((ops.layer_norm(ad, p[0], p[1], eps), ops.layer_norm(bd, p[2], p[3], eps)), dim=1)
+        else:
+            y = ops.layer_norm_concat(ad, p[0], p[1], eps, bd, p[2], p[3], eps)
+        _dirty_pool(a.shape)
+        y.backward(dy.to(DEV, BF))
+        return y.detach(), ad.grad, bd.grad, [t.grad for t in p]
+    y, da, db_in, pg = run(False)
+    ar, br = a.double().requires_grad_(True), b.double().requires_grad_(True)
+    pr = [t.double().requires_grad_(True) for t in (wa, ba, wb, bb)]
+    yr = torch.cat((R.layer_norm(ar, pr[0], pr[1], eps), R.layer_norm(br, pr[2], pr[3], eps)), dim=1)
+    yr.backward(dy.double())
+    tag = f"ln-paths {case['id']}"
+    out = [rowwise(tag + " y", y, yr.detach().view(-1, cols), k_all), rowwise(tag + " db_in", db_in, br.grad.view(-1, cols), kb)]
+    out += [metrics(tag + f" {nm}", g, r.grad.float(), TOL_GRAD) for nm, g, r in zip(("dgamma_a", "dbeta_a", "dgamma_b", "dbeta_b"), pg, pr)]
+    if a_grad:
+        out.append(rowwise(tag + " da_in", da, ar.grad.view(-1, cols), ka))
+    else:
+        out.append({"name": tag + " no gradient for a", "ok": da is None, "rel_l2": 0.0, "max_abs": 0.0, "tol": 0.0})
+    y2, da2, db2, pg2 = run(True)
+    out += [same_bits(tag + " y == cat of two LayerNorms", y, y2), same_bits(tag + " db_in == ATen form", db_in, db2)]
+    out += [same_bits(tag + f" {nm} == ATen form", g, g2) for nm, g, g2 in zip(("dgamma_a", "dbeta_a", "dgamma_b", "dbeta_b"), pg, pg2)]
+    if a_grad:
+        out.append(same_bits(tag + " da_in == ATen form", da, da2))
+    return out
+
+
+def finish_case(case_id, path, results):
+    """one row per case to $DVLA_PARITY_REPORT (worst rel-L2, worst element, slack used, the path the geometry says ran), every
+    metric printed, then the assertion"""
+    from tests.model_checks import report
+    sig = lambda v: float("%.4g" % v)
+    worst = max(results, key=lambda m: m.get("max_abs", 0.0))
+    row = {"case": case_id, "ok": all(m["ok"] for m in results), "checks": len(results), "rel_l2": sig(max(m.get("rel_l2", 0.0) for m in results)),
+           "max_abs": sig(worst.get("max_abs", 0.0)), "worst": worst["name"], "worst_index": worst.get("worst_index"),
+           "slack": sig(max(m.get("slack", 0.0) for m in results)), "allow_frac": sig(max(m.get("allow_frac", 0.0) for m in results)),
+           "path": path}
+    report([row])
+    for m in results:
+        print(("ok   " if m["ok"] else "FAIL ") + m["name"], {k: (sig(v) if isinstance(v, float) else v) for k, v in m.items()
+                                                               if k in ("rel_l2", "max_abs", "slack", "allow_frac", "allow_frac_row", "bad_rows",
+                                                                        "first_bad_row", "bad", "differing", "worst_index")})
+    bad = [m for m in results if not m["ok"]]
+    assert not bad, "; ".join(f"{m['name']}: " + ", ".join(f"{k}={m[k]}" for k in ("rel_l2", "max_abs", "slack", "allow_frac", "bad_rows",
+                                                                                  "first_bad_row", "bad", "differing", "worst_index") if k in m)
+                              for m in bad)
