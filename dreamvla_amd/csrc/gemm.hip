@@ -7,9 +7,9 @@
 #include "gemm_skinny.h"
 
 namespace dvla_gemm {
-#define DVLA_EXTERN_REG(CF, AT, BT, DBG) extern template void launch_one<CF, AT, BT, DBG>(const GemmKArgs&, int, hipStream_t);
+#define DVLA_EXTERN_REG(CF, AT, BT) extern template void launch_one<CF, AT, BT>(const GemmKArgs&, int, hipStream_t);
 #define DVLA_EXTERN_RING(RC, AT, BT, EPI) extern template void launch_ring_one<RC, AT, BT, EPI>(const GemmKArgs&, int, hipStream_t);
-#define DVLA_EXTERN_PHASE(AT, BT, EPI, DBG) extern template void launch_phase_one<AT, BT, EPI, DBG>(const GemmKArgs&, int, hipStream_t);
+#define DVLA_EXTERN_PHASE(AT, BT, EPI, FEAT) extern template void launch_phase_one<AT, BT, EPI, FEAT>(const GemmKArgs&, int, hipStream_t);
 #include "gemm_inst_list.h"
 #undef DVLA_EXTERN_REG
 #undef DVLA_EXTERN_RING
@@ -142,7 +142,8 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ ws, void* C, int6
   }
 }
 
-int g_gemm_variant = -1;   // 0 auto; force: 2 register-staged S, 4 / 5 / 6 / 7 ring 256^2 / 256x128 / 128^2 / 256x128 BK 64; 
+int g_gemm_variant = -1;   // 0 auto; force: 2 register-staged, 4 / 6 / 7 ring 256^2 / 128^2 / 256x128 BK 64, 8 / 9 / 10 phase (plain / stream-K
+                           // hybrid / full), 11 few-rows; any other number, or a configuration that does not take the problem: register-staged
 inline int gemm_variant() {
   if (g_gemm_variant < 0) {
     const char* e = getenv("DVLA_GEMM_VARIANT");
@@ -264,12 +265,12 @@ void launch_phase(GemmKArgs& a, int combo, int split_k, hipStream_t stream, int 
   set_tiles<PCfg::BM, PCfg::BN, PCfg::GH>(a);
   a.sk_tiles = 0;
   if (a.K % PCfg::BKS != 0) {       // partial last K-tile (phase_tail): its own instantiation, plain schedule
-    if (a.ksum_op != 0) launch_phase_one<true, true, EPI_F32, 128 | 8192>(a, split_k, stream);
-    else launch_phase_one<true, true, EPI_F32, 128>(a, split_k, stream);
+    if (a.ksum_op != 0) launch_phase_one<true, true, EPI_F32, PHASE_TAIL | PHASE_KSUM>(a, split_k, stream);
+    else launch_phase_one<true, true, EPI_F32, PHASE_TAIL>(a, split_k, stream);
     return;
   }
   if (a.ksum_op != 0) {             // k-sums: the TT layout's fp32 class with the summing code (phase_ok_ksum admits nothing else)
-    launch_phase_one<true, true, EPI_F32, 8192>(a, split_k, stream);
+    launch_phase_one<true, true, EPI_F32, PHASE_KSUM>(a, split_k, stream);
     return;
   }
   if (stream_k && split_k == 1 && a.ksum_op == 0) {     // (k-sums: one workgroup per (tile, K slice) owns a partial row)
@@ -313,7 +314,7 @@ bool ring_ok(const GemmKArgs& a, int combo) {
 }
 
 // the phase kernel addresses its operands as base + 32-bit byte offset: both must span less than 4 GiB
-// a contraction length that is not a multiple of the K-tile: the TT layout's fp32 class only (gemm_phase.h DBG & 128: the weight
+// a contraction length that is not a multiple of the K-tile: the TT layout's fp32 class only (gemm_phase.h PHASE_TAIL: the weight
 // gradients over 20 832 tokens), whole k16-steps, at least two K-tiles
 bool phase_tail(const GemmKArgs& a, int combo) {
   return a.K % PCfg::BKS != 0 && combo == 3 && epi_class(a) == EPI_F32 && a.K % 16 == 0 && a.K >= 2 * PCfg::BKS;
@@ -339,23 +340,8 @@ inline double fill(int64_t tiles, int64_t slots) {
 // what the last dvla_gemm_bf16 call of this process actually launched (tests assert that a forced configuration ran and did
 // not fall back): 2 register-staged, 4 / 6 / 7 ring 256^2 / 128^2 / 256x128, 8 phase (plain schedule), 9 / 10 phase with the
 // stream-K hybrid / full schedule ENGAGED (a stream-K request that does not apply reports 8); 0 = nothing launched yet
-// measurement variants of the phase kernel (tests/probes/gemm_probe.cpp; NN layout, plain bf16 epilogue only): 40 = the round-4
-// main loop (piece placement 13 + its issue code), 41 = its s_memtime build, 42 = placement 13 with the round-5 issue code,
-// 43 = every piece behind the fragment reads' wait
-static bool launch_phase_experiment(int idx, GemmKArgs& a, int split_k, hipStream_t stream) {
-  switch (idx) {
-    case 0: launch_phase_one<false, false, 0, 7424>(a, split_k, stream); return true;
-    case 1: launch_phase_one<false, false, 0, 7488>(a, split_k, stream); return true;
-    case 2: launch_phase_one<false, false, 0, 3328>(a, split_k, stream); return true;
-    case 3: launch_phase_one<false, false, 0, 256>(a, split_k, stream); return true;
-    case 4: launch_phase_one<false, false, 0, 32768>(a, split_k, stream); return true;            // 44: round-5 boundary, buffer-descriptor DMA
-    case 5: launch_phase_one<false, false, 0, 16384 | 65536>(a, split_k, stream); return true;    // 45: deferred epilogue, fragment addresses hoisted
-    case 6: launch_phase_one<false, false, 0, 16384 | 65536 | 131072>(a, split_k, stream); return true;    // 46: 45 + the in-loop epilogue at priority 2
-    case 7: launch_phase_one<false, false, 0, 16384>(a, split_k, stream); return true;                      // 47: deferred epilogue as first measured (fragment addresses re-derived per K-tile)
-    default: return false;
-  }
-}
-
+// 89 (only in a build with -DDVLA_GEMM_STAMPS): the phase kernel's s_memtime build, NN layout, plain bf16 epilogue
+// (tests/probes/gemm_probe.cpp --stamps)
 static int g_last_variant = 0;
 extern "C" int dvla_last_gemm_variant(void) { return g_last_variant; }
 extern "C" void dvla_set_gemm_variant(int v) { g_gemm_variant = v; }
@@ -442,7 +428,6 @@ extern "C" int dvla_gemm_bf16(const dvla_gemm_params* q, void* stream_) {
 
   const int combo = (q->a_trans ? 2 : 0) | (q->b_trans ? 1 : 0);
   int variant = gemm_variant();
-  if (variant >= 100) variant %= 100;   // (hundreds digit: reserved for A/B knobs of measurement builds)
   {
     // Configuration choice: cheapest by a two-constant model per configuration, T = rounds * (fixed + stage * ns),
     // rounds = ceil(work items / workgroup slots), ns = 32-wide K stages per item.  Constants in microseconds per round,
@@ -484,8 +469,9 @@ extern "C" int dvla_gemm_bf16(const dvla_gemm_params* q, void* stream_) {
     else if (variant == 8 && phase_ok(a, combo)) choice = 5;
     else if (variant == 9 && phase_ok(a, combo)) choice = 6;
     else if (variant == 10 && phase_ok(a, combo)) choice = 7;
-    else if (variant > 80 && variant < 90 && combo == 0 && phase_ok(a, combo)) choice = 80 + (variant - 80);
-    else if (variant >= 40 && variant < 48 && combo == 0 && phase_ok(a, combo) && epi_class(a) == EPI_P0) choice = variant;
+#ifdef DVLA_GEMM_STAMPS
+    else if (variant == 89 && combo == 0 && phase_ok(a, combo)) choice = 89;
+#endif
     // k-sums ride on the ring kernels and (round 5) on the phase kernel of the fp32-output class (split-K partial sums or fp32 C:
     // the weight gradients); the other configurations get the column-sum kernel below
     const bool phase_choice = choice == 5 || choice == 6 || choice == 7;
@@ -506,27 +492,17 @@ extern "C" int dvla_gemm_bf16(const dvla_gemm_params* q, void* stream_) {
       case 6: launch_phase(a, combo, split_k, stream, 1); break;   // falls back to the plain schedule when stream-K does not apply
       case 7: launch_phase(a, combo, split_k, stream, 2); break;
       case 11: launch_skinny(a, stream); break;
-      case 81: case 83: case 84: case 85: case 86: case 88: case 89:   // ablations (plain bf16 epilogue only): 81 no MFMA, 83 no MFMA + no reads, 84 no DMA, 85 no epilogue, 86 raw stores only
+#ifdef DVLA_GEMM_STAMPS
+      case 89:      // s_memtime stamps into p.workspace
         set_tiles<PCfg::BM, PCfg::BN, PCfg::GH>(a);
         if (epi_class(a) != EPI_P0) return DVLA_ERR_UNSUPPORTED;
-        if (choice == 81) launch_phase_one<false, false, 0, 1>(a, split_k, stream);
-        else if (choice == 83) launch_phase_one<false, false, 0, 3>(a, split_k, stream);
-        else if (choice == 84) launch_phase_one<false, false, 0, 4>(a, split_k, stream);
-        else if (choice == 85) launch_phase_one<false, false, 0, 16>(a, split_k, stream);
-        else if (choice == 86) launch_phase_one<false, false, 0, 32>(a, split_k, stream);
-        else if (choice == 88) launch_phase_one<false, false, 0, 16448>(a, split_k, stream);   // 88: the stamps build of the deferred epilogue
-        else launch_phase_one<false, false, 0, 64>(a, split_k, stream);   // 89: s_memtime stamps into p.workspace
+        launch_phase_one<false, false, EPI_P0, PHASE_STAMPS>(a, split_k, stream);
         break;
-      default:
-        if (choice >= 40 && choice < 48) {
-          set_tiles<PCfg::BM, PCfg::BN, PCfg::GH>(a);
-          a.sk_tiles = 0;
-          if (launch_phase_experiment(choice - 40, a, split_k, stream)) break;
-        }
-        launch_cfg<CfgS>(a, combo, split_k, stream); break;
+#endif
+      default: launch_cfg<CfgS>(a, combo, split_k, stream); break;
     }
     g_last_variant = choice == 11 ? 11 : choice == 1 ? 4 : choice == 3 ? 6 : choice == 4 ? 7 : choice == 5 ? 8
-                   : (choice == 6 || choice == 7) ? (a.sk_tiles > 0 ? (choice == 6 ? 9 : 10) : 8) : choice >= 80 ? choice : 2;
+                   : (choice == 6 || choice == 7) ? (a.sk_tiles > 0 ? (choice == 6 ? 9 : 10) : 8) : choice == 89 ? 89 : 2;
   }
   int rc = dvla_check_launch();
   if (rc != DVLA_OK) return rc;

@@ -456,7 +456,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmKArgs& p, f32x16 (&acc)[
   });
 }
 
-template <class CF, bool A_T, bool B_T, int DBG = 0>
+template <class CF, bool A_T, bool B_T>
 __global__ __launch_bounds__(CF::NT) void gemm_kernel(GemmKArgs p) {
   constexpr int BM = CF::BM, BN = CF::BN, TM = CF::TM, TN = CF::TN;
   extern __shared__ __attribute__((aligned(16))) char smem[];  // [buf][A|B]
@@ -537,19 +537,18 @@ __global__ __launch_bounds__(CF::NT) void gemm_kernel(GemmKArgs p) {
       // steady state, no conditionals inside: the compiler can then count the 8 newer loads and wait with vmcnt(8)
       // (a conditional prefetch forces s_waitcnt vmcnt(0) at the join and serialises load latency with the MFMAs)
       while (kt + 3 < nk_full) {
-        // DBG (ablation builds only): 1 = no global loads / LDS writes, 2 = no MFMAs, 4 = no barriers
-        if (!(DBG & 1)) { fast_load<A_T>(ra0, pa, p.lda); fast_load<B_T>(rb0, pb, p.ldb); }
+        fast_load<A_T>(ra0, pa, p.lda); fast_load<B_T>(rb0, pb, p.ldb);
         __builtin_amdgcn_sched_barrier(0);  // issue the prefetch BEFORE the MFMAs (the scheduler would sink it)
-        if (!(DBG & 2)) compute(buf0);
+        compute(buf0);
         __builtin_amdgcn_sched_barrier(0);  // keep the ds_writes (and their vmcnt wait) BEHIND the MFMAs
-        if (!(DBG & 1)) store_tile(ra1, rb1, buf1);
-        if (!(DBG & 4)) __syncthreads();
-        if (!(DBG & 1)) { fast_load<A_T>(ra1, pa, p.lda); fast_load<B_T>(rb1, pb, p.ldb); }
+        store_tile(ra1, rb1, buf1);
+        __syncthreads();
+        fast_load<A_T>(ra1, pa, p.lda); fast_load<B_T>(rb1, pb, p.ldb);
         __builtin_amdgcn_sched_barrier(0);
-        if (!(DBG & 2)) compute(buf1);
+        compute(buf1);
         __builtin_amdgcn_sched_barrier(0);
-        if (!(DBG & 1)) store_tile(ra0, rb0, buf0);
-        if (!(DBG & 4)) __syncthreads();
+        store_tile(ra0, rb0, buf0);
+        __syncthreads();
         kt += 2;
       }
     }
@@ -684,30 +683,17 @@ __device__ __forceinline__ const bf16_t* dma_src(const bf16_t* __restrict__ P, i
   }
 }
 
-// One LDS-DMA instruction, issued from inline asm so that hipcc does not count it (it would otherwise put an
-// s_waitcnt vmcnt(0) in front of the next ds_read and serialise the ring).  M0 (LDS base of the transfer) is saved and
-// restored inside the statement (cdna guide section 5.7).  lds_dst must be wave-uniform.
-__device__ __forceinline__ void glds16(const void* gsrc, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-
-// the same from a wave-uniform base (SGPR pair) + a per-lane 32-bit byte offset
-__device__ __forceinline__ void glds16s(const void* sbase, uint32_t voff, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-
-// Round 5, the phase kernel's piece issue: M0 = <LDS address of the wave's piece 0 of the image> + IMM in ONE scalar add, the hazard
-// nop, the DMA -- M0 is NOT saved / restored.  Legal only in a kernel none of whose other instructions reads M0:
-// tests/test_phase_isa.py disassembles every gemm_phase_kernel of the built library and asserts exactly that.
+// One LDS-DMA instruction from a wave-uniform base (SGPR pair) + a per-lane 32-bit byte offset, issued from inline asm so that
+// hipcc does not count it (it would otherwise put an s_waitcnt vmcnt(0) in front of the next ds_read and serialise the ring).
+// M0 (LDS base of the transfer; lds_dst must be wave-uniform) is written and NOT saved / restored (round 5).  Legal only in a
+// kernel none of whose other instructions reads M0: tests/test_phase_isa.py disassembles every DMA kernel of the built library
+// and asserts exactly that.
 // the ring kernels' form: the LDS address is a scalar the loop already holds (stage base + the wave's piece offset)
 __device__ __forceinline__ void glds16s_m0(const void* sbase, uint32_t voff, uint32_t lds_dst) {
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
                : : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
 }
+// the phase kernel's form: M0 = <LDS address of the wave's piece 0 of the image> + IMM in ONE scalar add, the hazard nop, the DMA.
 // PAD (round 6): wait states between the M0 write and the DMA.  0 is the M0 hazard alone.  hipcc may reload a spilled SGPR (the scalar
 // base) with v_readlane_b32 right in front of the statement, and an SGPR written by the VALU needs FIVE wait states before a VMEM
 // instruction reads it -- padding hipcc does for its own instructions, not for these.  tests/test_phase_isa.py audits every built kernel
@@ -716,24 +702,6 @@ template <int IMM, int PAD = 0>
 __device__ __forceinline__ void glds16s_lean(const void* sbase, uint32_t voff, uint32_t lds_base) {
   asm volatile("s_add_u32 m0, %2, %3\n\ts_nop %4\n\tglobal_load_lds_dwordx4 %0, %1"
                : : "v"(voff), "s"(sbase), "s"(lds_base), "n"(IMM), "n"(PAD) : "memory", "scc");
-}
-
-// Round 6, the deferred-epilogue builds: the same piece through a BUFFER descriptor over the whole operand -- address = base + per-lane
-// offset + scalar offset, rows past the operand's end are refused by the descriptor's bounds check (no per-lane clamp), so a wave's
-// four pieces of an image need two per-lane offsets (even / odd piece: the swizzle alternates) and scalar offsets instead of four
-// per-lane offsets and the hoisted row / column parts they were built from (gemm_phase.h BUFDMA).  soff must have been written well
-// ahead of the statement (an SGPR written by the SALU needs five wait states in front of a VMEM instruction that reads it).
-typedef __attribute__((ext_vector_type(4))) uint32_t rsrc4;
-__device__ __forceinline__ rsrc4 operand_rsrc(const void* base, uint64_t bytes) {
-  const uint64_t a = reinterpret_cast<uint64_t>(base);
-  return rsrc4{(uint32_t)a, (uint32_t)(a >> 32) & 0xffffu, bytes > 0xffffffffull ? 0xffffffffu : (uint32_t)bytes, 0x00020000u};
-}
-template <int IMM>
-__device__ __forceinline__ void glds16b_lean(rsrc4 rs, uint32_t voff, uint32_t soff, uint32_t lds_base) {
-  // (s_nop 3: with the s_add in front, five wait states between a compiler reload of rs / soff -- v_readlane_b32 of a spilled SGPR,
-  //  which hipcc may place right in front of the statement and does not pad for instructions it cannot see -- and the VMEM read)
-  asm volatile("s_add_u32 m0, %3, %4\n\ts_nop 3\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
-               : : "v"(voff), "s"(rs), "s"(soff), "s"(lds_base), "n"(IMM) : "memory", "scc");
 }
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
@@ -947,9 +915,7 @@ __device__ __forceinline__ u32x4 window_load(const RowWindow& w, int row) {
 }
 
 struct NoStamp { __device__ __forceinline__ void operator()(int) const {} };   // timeline builds pass a recorder instead
-// NO_BIAS: the bias is already inside the accumulators (the phase kernel's deferred-epilogue builds fold it in with one MFMA per
-// accumulator block, gemm_phase.h)
-template <int TM, int EPI, class ST = NoStamp, bool NO_BIAS = false>
+template <int TM, int EPI, class ST = NoStamp>
 __device__ __forceinline__ void reg_epilogue(const GemmKArgs& p, f32x16 (&acc)[2][TM], int lane, int64_t m_base,
                                              int64_t n_base, int split, ST st = ST()) {
   if (n_base >= p.N) return;   // N % 64 == 0: a wave's 64 columns are all inside or all outside
@@ -961,7 +927,7 @@ __device__ __forceinline__ void reg_epilogue(const GemmKArgs& p, f32x16 (&acc)[2
   constexpr bool f32_out = EPI == EPI_F32;
   const bool has_dact = epi_dact(EPI) > 0 || (epi_dact(EPI) < 0 && p.dact_aux != nullptr);
   const bool has_res = epi_res(EPI) > 0 || (epi_res(EPI) < 0 && p.residual != nullptr);
-  const bool has_bias = !NO_BIAS && !split_out && p.bias != nullptr;
+  const bool has_bias = !split_out && p.bias != nullptr;
   const bool two_aux = has_dact && has_res;   // none of the model's GEMMs has both: the act' operand is then read late
 
   // ================= split-K partial sums (the weight gradients): whole 128-byte lines of fp32 =================
@@ -1331,55 +1297,6 @@ __device__ __forceinline__ void reg_epilogue(const GemmKArgs& p, f32x16 (&acc)[2
   });
 }
 
-// ================= pieces of the phase kernel's DEFERRED epilogue (round 6, gemm_phase.h) =================
-// The phase kernel's tile boundary was 16-22 % of a K = 1024 launch with the matrix pipe idle (profiles/r05_gemm_epilogue_decomposition.txt).
-// Its deferred builds run the epilogue of tile t at the head of the next tile's first load segment, one wave group at a time, while
-// the partner wave of the SIMD multiplies (gemm_phase.h DEFER).  The pieces below are what that path needs.
-//
-// Loads the compiler must not count (as the LDS-DMA pieces: its own s_waitcnt in front of the first use would be computed without
-// the DMA pieces issued in between and drain them): issued from inline asm, waited for by wait_vmcnt_dyn + settle.
-// (s_nop 4: an SGPR written by a VALU instruction -- hipcc reloads spilled SGPRs with v_readlane_b32, possibly right in front of the
-// statement -- needs five wait states before a VMEM instruction reads it; hipcc pads that only for instructions it can see.  The
-// first build without the nops read the bias through a stale base register: memory faults in every erf-GELU launch.
-// tests/probes/asm_hazard_audit.py checks the compiler's assembly for this pattern.)
-__device__ __forceinline__ uint32_t aload_b32(const void* sbase, uint32_t voff) {
-  uint32_t r;
-  asm volatile("s_nop 4\n\tglobal_load_dword %0, %1, %2" : "=v"(r) : "v"(voff), "s"(sbase) : "memory");
-  return r;
-}
-__device__ __forceinline__ uint32_t aload_u16(const void* sbase, uint32_t voff) {
-  uint32_t r;
-  asm volatile("s_nop 4\n\tglobal_load_ushort %0, %1, %2" : "=v"(r) : "v"(voff), "s"(sbase) : "memory");
-  return r;
-}
-__device__ __forceinline__ void settle(uint32_t& a, uint32_t& b) { asm volatile("" : "+v"(a), "+v"(b) :: "memory"); }
-// s_waitcnt vmcnt(n) for a wave-uniform n = 0, 4, 8, ... 60 (the immediate is six bits); other values round DOWN (waits for more)
-__device__ __forceinline__ void wait_vmcnt_dyn(int n) {
-  switch (n >> 2) {
-    case 0: wait_vmcnt<0>(); break;   case 1: wait_vmcnt<4>(); break;   case 2: wait_vmcnt<8>(); break;   case 3: wait_vmcnt<12>(); break;
-    case 4: wait_vmcnt<16>(); break;  case 5: wait_vmcnt<20>(); break;  case 6: wait_vmcnt<24>(); break;  case 7: wait_vmcnt<28>(); break;
-    case 8: wait_vmcnt<32>(); break;  case 9: wait_vmcnt<36>(); break;  case 10: wait_vmcnt<40>(); break; case 11: wait_vmcnt<44>(); break;
-    case 12: wait_vmcnt<48>(); break; case 13: wait_vmcnt<52>(); break; case 14: wait_vmcnt<56>(); break; default: wait_vmcnt<60>(); break;
-  }
-}
-// The bias as ONE extra multiply per accumulator block: acc[n][m] += sum_k F[n][k] . O[m][k] with F[n][0..2] = a three-way bf16 split of
-// bias[n] (hi + mid + lo == the fp32 value: 3 x 8 significant bits; a bf16 bias is its own `hi`) and O[m][0..2] = 1 -- k = 0..3 live in
-// the lower half-wave of a v_mfma_f32_32x32x8_bf16_1k operand, the upper half-wave holds zeros.  128 v_add per tile and wave (and the
-// bias registers they read) become 8 short MFMAs.
-typedef __attribute__((ext_vector_type(4))) short bf16x4v;
-__device__ __forceinline__ bf16x4v bias_split(float b, bool lower_half) {
-  const float b0 = lower_half ? b : 0.f;
-  const bf16_t hi = f2bf(b0);
-  const float r1 = b0 - bf2f(hi);
-  const bf16_t mid = f2bf(r1);
-  const bf16_t lo = f2bf(r1 - bf2f(mid));
-  return bf16x4v{(short)hi, (short)mid, (short)lo, 0};
-}
-__device__ __forceinline__ bf16x4v bias_ones(bool lower_half) {
-  const short one = lower_half ? (short)0x3f80 : (short)0;
-  return bf16x4v{one, one, one, 0};
-}
-
 template <class RC, bool A_T, bool B_T, int EPI>
 __global__ __launch_bounds__(RC::NT) __attribute__((amdgpu_waves_per_eu(RC::WPE, RC::WPE)))
 void gemm_ring_kernel(GemmKArgs p) {
@@ -1556,10 +1473,10 @@ inline int num_cus() {
   return n;
 }
 
-template <class CF, bool A_T, bool B_T, int DBG = 0>
+template <class CF, bool A_T, bool B_T>
 void launch_one(const GemmKArgs& a, int split_k, hipStream_t stream) {
   static bool attr_set = false;
-  auto kern = &gemm_kernel<CF, A_T, B_T, DBG>;
+  auto kern = &gemm_kernel<CF, A_T, B_T>;
   if (!attr_set) {  // > 64 KiB of LDS per workgroup needs the opt-in (160 KiB per CU on gfx950)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM_BYTES);
     attr_set = true;

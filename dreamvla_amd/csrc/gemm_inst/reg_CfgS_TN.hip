@@ -1,2 +1,2 @@
 #include "../gemm_impl.h"
-namespace dvla_gemm { template void launch_one<CfgS, true, false, 0>(const GemmKArgs&, int, hipStream_t); }
+namespace dvla_gemm { template void launch_one<CfgS, true, false>(const GemmKArgs&, int, hipStream_t); }

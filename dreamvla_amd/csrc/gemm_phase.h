@@ -17,27 +17,39 @@
 //       LOAD2: fragments a-hi into the a-lo registers
 //       MFMA2: 16 MFMAs (a-hi x B, B fragments still in registers)
 //     and this wave's 4 DMA pieces of the A image of tile u+2 (slot (u+2) % 3: last read in LOAD2(u-1)) and 4 of the B image
-//     of tile u+2 (buffer u&1: its B fragments were all read in LOAD1(u), by both groups -- hence from LOAD2 on).  Rounds 2-4
-//     spread them over the four segments (LOAD1: A0 | MFMA1: A1 A2 | LOAD2: A3 B0 | MFMA2: B1 B2 B3); round 5 issues them at
-//     the head of the two load segments, in three instructions each (piece_place / LEAN below: +15 % at 8192^3).
+//     of tile u+2 (buffer u&1: its B fragments were all read in LOAD1(u), by both groups -- hence from LOAD2 on).  The A pieces
+//     are issued at the head of LOAD1, the B pieces at the head of LOAD2, in three instructions each ("DMA piece placement"
+//     and pieceA / pieceB below).
 //     every ds_read of a segment is waited for (lgkmcnt(0)) BEFORE the barrier that ends the segment -- the wait is hidden
 //     under the partner's MFMA segment -- so "read in segment s" means "retired by the end of s", which is what the refill
 //     rule above needs.  RAW: at the end of MFMA2(u) every wave waits vmcnt(8): all of its pieces except the eight it issued
 //     during tile u (A(u+2), B(u+2)) have landed, i.e. A(u+1) and B(u+1); group 1 (whose MFMA2(u) ends one slot after group 0
-//     starts reading tile u+1) waits for the same pieces at the end of its LOAD2(u) (vmcnt(n): the n pieces of tile u issued so far are
-//     younger -- pieces_up_to() of the placement table).  The barriers publish.  Both operands run two tiles ahead: three A images (tile u in slot u % 3) and two B
-//     images (whose fragments are all read in LOAD1 and which are therefore free again from LOAD2 on): 160 KiB of LDS.
+//     starts reading tile u+1) waits for the same pieces at the end of its LOAD2(u) (vmcnt(8) as well: all eight pieces of
+//     tile u have been issued by then and are younger).  The barriers publish.  Both operands run two tiles ahead: three A
+//     images (tile u in slot u % 3) and two B images (whose fragments are all read in LOAD1 and which are therefore free again
+//     from LOAD2 on): 160 KiB of LDS.
 //   The DMA stream never stops at an output-tile boundary (two cursors walk the work-item list ahead of the multiply); at a
 //   boundary the groups re-align with one extra barrier, run the register-only epilogue at the same time and re-stagger.
 //
 // Requirements (dispatcher falls back otherwise): as ring_ok with BKS = 64: 16-B-vectorisable operands / outputs,
 // K-range % 64 == 0, N % 64 == 0, M >= 256, N >= 256, r-contiguous operands with rows % 256 == 0.
-// DBG & 128 (round 4, the TT layout's fp32 class = the weight gradients): K % 64 may be 16 / 32 / 48 -- the trunk's weight
+//
+// The kernel's last template argument FEAT is a set of features (bits below); 0 is the plain kernel.
+// PHASE_TAIL (round 4, the TT layout's fp32 class = the weight gradients): K % 64 may be 16 / 32 / 48 -- the trunk's weight
 // gradients contract over 20 832 = 651 x 32 tokens and ran on the BK-32 ring kernel at 775-850 TFLOP/s where this kernel runs the
 // same problem class at 1 200-1 300 (profiles/r03_gemm_breakdown.json).  The last K-tile of the last K slice is then partial:
 // its DMA pieces that would read k rows past the operand are pointed at the tile's first row instead (same count of pieces:
 // the counted waits do not change), and the A fragments of its dead k16-steps are zeroed after the fragment reads have
 // retired, so whatever the B fragments of those steps hold is multiplied by zero.
+// PHASE_KSUM: the fused k-sums (dvla.h ksum_*), fp32 class only -- "k-sums" inside the kernel.
+// PHASE_STAMPS: the measurement build (NN layout, plain class; compiled only with -DDVLA_GEMM_STAMPS): s_memtime stamps at the
+// segment edges, the tile boundaries and the boundary epilogue's slabs, read by tests/probes/gemm_probe.cpp --stamps.
+//
+// Measured, written up and removed (DESIGN.md section 4.1 has the results; the code is in the history):
+//   the ablation builds (no MFMAs / fragment reads / DMA / barriers / epilogue)     profiles/r02_gemm_phase_ablation.txt, r06_gemm_energy_ablation.txt
+//   other piece placements and the round-4 twelve-instruction piece issue          profiles/r05_gemm_placement_probe*.txt, r05_gemm_probe_nn_vs_round4.txt
+//   the deferred epilogue (zero-C multiplies, accumulators carried across tiles)   profiles/r06_gemm_defer_ab.txt, r06_gemm_defer_stamps.txt
+//   DMA pieces through a buffer descriptor                                         the same
 #pragma once
 #include "gemm_impl.h"
 
@@ -53,27 +65,22 @@ struct PCfg {
   static constexpr int CPW = 4;                      // DMA pieces (1 KiB each) per wave and operand image
 };
 
-// Where in a K-tile a wave issues its eight LDS-DMA pieces (A0..A3 of image A(u+2): legal anywhere in tile u; B0..B3 of image
-// B(u+2): from LOAD2 on -- file header).  Slots: 0 / 1 / 2 = LOAD1 before the fragment reads / behind them / behind their
-// lgkmcnt(0); 3..6 = MFMA1 behind k16-step 0..3; 7 / 8 / 9 = LOAD2 likewise; 10..13 = MFMA2 behind k16-step 0..3.  Pieces of an
-// operand must be in non-decreasing slot order (the cursor advances behind the fourth).  PL = (DBG >> 8) & 15 selects the table.
-// Round 5 (profiles/r05_gemm_placement_probe*.txt, 12 placements x {round-4 issue code, three-instruction issue}, NN plain,
-// same-process A/B): with every piece in a LOAD segment IN FRONT of the fragment reads the multiply segments are 568-588 cycles
-// (512 of MFMA) instead of 700-880 with two or three pieces between their MFMAs, and the load segments still fit beside them --
-// the four waves of a group issue their pieces at the same point of the program, the CU's one address path takes them one after
-// the other (16 cycles per 1-KiB piece), and what a piece costs the ISSUING wave is its place in that queue: harmless in a wave
-// that is about to wait for LDS anyway, ~100 cycles of idle matrix pipe in a wave that is multiplying.  8192^3: 1 272 -> 1 405
-// TFLOP/s from the placement alone, -> 1 490 together with the three-instruction issue (below); K = 1024: 992 -> 1 192.
+// DMA piece placement: a wave issues its four pieces of image A(u+2) at the head of LOAD1(u) and its four of B(u+2) at the head of
+// LOAD2(u) (the earliest legal point: file header), both IN FRONT of the segment's fragment reads.  Round 5
+// (profiles/r05_gemm_placement_probe*.txt, same-process A/B): with every piece in a LOAD segment in front of the fragment reads
+// the multiply segments are 568-588 cycles (512 of MFMA) instead of 700-880 with two or three pieces between their MFMAs, and
+// the load segments still fit beside them -- the four waves of a group issue their pieces at the same point of the program,
+// the CU's one address path takes them one after the other (16 cycles per 1-KiB piece), and what a piece costs the ISSUING
+// wave is its place in that queue: harmless in a wave that is about to wait for LDS anyway, ~100 cycles of idle matrix pipe in
+// a wave that is multiplying.  8192^3: 1 272 -> 1 405 TFLOP/s from the placement alone, -> 1 490 together with the
+// three-instruction issue (pieceA below); K = 1024: 992 -> 1 192.
+// The placement as a table (slot of pieces A0..A3, B0..B3; 0 = head of LOAD1, 7 = head of LOAD2) and the number of pieces issued up
+// to a slot.  Only two things still read it: group 1's counted wait in LOAD2 and the never-taken statements at the end of the two
+// multiply lambdas -- see the note there on why those are kept.
 struct PiecePlace { int slot[8]; };
 __device__ __forceinline__ constexpr std::true_type live_or(std::true_type, bool) { return {}; }
 __device__ __forceinline__ constexpr bool live_or(std::false_type, bool live) { return live; }
-__host__ __device__ constexpr PiecePlace piece_place(int pl) {
-  switch (pl) {
-    case 1:  return {{2, 2, 2, 2, 9, 9, 9, 9}};        // everything behind the fragment reads' wait, in front of the barrier (-1 ... -3 %)
-    case 13: return {{1, 4, 6, 8, 8, 11, 12, 13}};     // rounds 2-4: LOAD1: A0 | MFMA1: A1 A2 | LOAD2: A3 B0 | MFMA2: B1 B2 B3 (-7 %)
-    default: return {{0, 0, 0, 0, 7, 7, 7, 7}};        // production: in front of the fragment reads of the two load segments
-  }
-}
+__host__ __device__ constexpr PiecePlace piece_place(int) { return {{0, 0, 0, 0, 7, 7, 7, 7}}; }
 __host__ __device__ constexpr int pieces_up_to(int pl, int slot) {
   int n = 0;
   for (int i = 0; i < 8; ++i) n += piece_place(pl).slot[i] <= slot ? 1 : 0;
@@ -86,31 +93,18 @@ __host__ __device__ constexpr int pieces_up_to(int pl, int slot) {
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t sk_rsrc(float* slab) {
   return __builtin_amdgcn_make_buffer_rsrc(slab, 0, PCfg::BM * PCfg::BN * 4, 0x00020000);
 }
-// DBG (ablation builds, results are garbage by design; variants 81..86 of the NT layout): 1 = no MFMAs, 2 = no fragment
-// reads, 4 = no DMA, 8 = no barriers inside the K loop
-template <bool A_T, bool B_T, int EPI, int DBG = 0>
+constexpr int PHASE_STAMPS = 64, PHASE_TAIL = 128, PHASE_KSUM = 8192;     // the bits of gemm_phase_kernel's FEAT (file header)
+
+template <bool A_T, bool B_T, int EPI, int FEAT = 0>
 __global__ __launch_bounds__(PCfg::NT) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void gemm_phase_kernel(GemmKArgs p) {
   constexpr int BM = PCfg::BM, BN = PCfg::BN, BKS = PCfg::BKS, CPW = PCfg::CPW;
-  constexpr bool TAIL = (DBG & 128) != 0;
-  constexpr int PL = (DBG >> 8) & 15;
-  // DEFER (DBG & 16384, round 6; the P classes): the epilogue of a whole tile (kind 0) that has a successor runs at the head of LOAD1 of
-  // the NEXT tile's first K-tile -- every fragment register is dead there, the accumulators are complete, and the partner group is in a
-  // multiply segment (group 0's epilogue beside group 1's MFMA2 of the old tile, group 1's beside group 0's MFMA1 of the new one: the
-  // VALU and the CU's store path serve ONE group at a time instead of both with the matrix pipe idle) -- and that K-tile's MFMA1 / MFMA2
-  // overwrite the accumulator halves through a zero C operand (no zeroing).  The groups keep their one-segment skew across such a
-  // boundary: no re-align / re-stagger barriers, no drain of the DMA queue.  The bias enters the accumulators as one short MFMA per
-  // block in the first K-tile (no bias registers, no adds in the epilogue).
-  constexpr bool DEFER = (DBG & 16384) != 0;
-  // ZC (the deferred builds): the first k16-step of a segment's first K-tile multiplies into a literal-zero C operand instead of 128
-  // accumulator registers zeroed by the VALU at every tile top.  (On its own -- the product loop with its two copies, per-tile
-  // accumulators left undefined -- hipcc spills 691 registers around the first-K-tile branches: not a separable piece.)
-  constexpr bool ZC = DEFER;
-  static_assert(!(DBG & 32768) || (!TAIL && (DBG & 4096) == 0), "buffer DMA path: lean issue code, whole K-tiles");
-  static_assert(!DEFER || (!TAIL && (DBG & (4096 | 8192)) == 0 && PL == 0 && (EPI == EPI_P0 || EPI == EPI_P_ERF || EPI == EPI_P_TANH)),
-                "deferred epilogue: production loop, P classes");
+  constexpr bool TAIL = (FEAT & PHASE_TAIL) != 0, STAMPS = (FEAT & PHASE_STAMPS) != 0;
+  static_assert((FEAT & ~(PHASE_TAIL | PHASE_KSUM | PHASE_STAMPS)) == 0, "unknown feature bit");
+  static_assert(!(FEAT & PHASE_KSUM) || EPI == EPI_F32, "k-sums: fp32 class only");
+  constexpr int PL = 0;          // the one placement (piece_place)
+  constexpr bool ZC = false;     // see the note in MFMA1
   static_assert(!TAIL || (A_T && B_T), "partial K-tiles: k-major operands only");
-  static_assert(piece_place(PL).slot[4] >= 7, "B pieces: from LOAD2 on");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int t = threadIdx.x;
   const int lane = t & 63;
@@ -189,12 +183,12 @@ void gemm_phase_kernel(GemmKArgs p) {
     return true;
   };
   const uint32_t smem_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  // CACHE (off in the DBG & 4096 build): one decode of a work segment per tile instead of four.  A segment index is decoded by the multiply loop
-  // (its own tile), by the look-ahead test of the LEAN build (the next one) and by both DMA cursors when they cross into the next
+  // CACHE: one decode of a work segment per tile instead of four.  A segment index is decoded by the multiply loop (its own tile),
+  // by the look-ahead test in front of the K loop (the next one) and by both DMA cursors when they cross into the next
   // segment -- ~150 dependent scalar instructions each (ring_item: three divisions by reciprocal, one real division by the ragged
   // raster height), all of them on the tile boundary's critical path.  The tile top decodes segment it + 1 once and keeps it.
   // (not in the partial-K-tile build that also carries k-sums: at the register limit, and its segments are 80+ K-tiles long)
-  constexpr bool CACHE = (DBG & 4096) == 0 && !((DBG & 128) != 0 && (DBG & 8192) != 0);
+  constexpr bool CACHE = !(TAIL && (FEAT & PHASE_KSUM) != 0);
   Seg c_seg = {0, 0, 0, 0, 0, 0};
   int c_it = -1;
   bool c_ok = false;
@@ -220,53 +214,21 @@ void gemm_phase_kernel(GemmKArgs p) {
   int tvA = 4, tvB = 4;                                         // tail_steps of the segments the cursors are in
   const uint32_t stepA = (uint32_t)(2 * (A_T ? (int64_t)BKS * p.lda : (int64_t)BKS));
   const uint32_t stepB = (uint32_t)(2 * (B_T ? (int64_t)BKS * p.ldb : (int64_t)BKS));
-  // LEAN (every build but DBG & 4096): a piece is THREE instructions -- `s_add_u32 m0, <LDS address of this wave's piece 0 of the image>, 1024 i`,
-  // the hazard nop, the DMA -- instead of ~12 (liveness branch, shift + add for the LDS address, M0 saved / set / restored, the
-  // per-lane source advanced by a v_add + v_mov).  The K position lives in the SCALAR base of the instruction (one s_add_u32 +
-  // s_addc_u32 per operand and K-tile) and the per-lane offsets stay what openA / openB computed; M0 is not restored (no
-  // instruction of these kernels reads it: tests/test_phase_isa.py); the liveness test is made once per TILE (two copies of the K
-  // loop, see kloop below -- two copies of the K-tile BODY inside one loop made the register allocator spill the accumulators).
-  constexpr bool LEAN = (DBG & 4096) == 0;        // DBG & 4096: the round-4 issue code (measurement variant 40 of gemm.hip)
+  // A piece is THREE instructions -- `s_add_u32 m0, <LDS address of this wave's piece 0 of the image>, 1024 i`, the hazard nop,
+  // the DMA (gemm_impl.h glds16s_lean).  The K position lives in the SCALAR base of the instruction (one s_add_u32 + s_addc_u32
+  // per operand and K-tile) and the per-lane offsets stay what openA / openB computed; M0 is not restored (no instruction of
+  // these kernels reads it: tests/test_phase_isa.py); the liveness test is made once per TILE (two copies of the K loop, see
+  // kloop below -- two copies of the K-tile BODY inside one loop made the register allocator spill the accumulators).
   const char* kbA = reinterpret_cast<const char*>(p.A);
   const char* kbB = reinterpret_cast<const char*>(p.B);
   uint32_t m0A = smem_base + (uint32_t)(wave * (CPW * 1024));
   uint32_t m0B = m0A + (uint32_t)PCfg::B_BASE;
-  // BUFDMA (the deferred-epilogue builds): pieces through a buffer descriptor over the whole operand (gemm_impl.h glds16b_lean).
-  // Piece i of this wave = voX[i & 1] (per lane, relative to the segment's origin) + soX / soX2 (scalar: origin + K position, for
-  // pieces 0-1 / 2-3).  k-contiguous operand: piece c = 4 wave + i holds rows 8 c + lane / 8, slot lane % 8 swizzled by
-  // (row >> 1) & 7 = (lane >> 4) + 4 (i & 1); r-contiguous: k rows 2 c + lane / 32, slot lane % 32 swizzled by 4 (k & 3) =
-  // 4 (2 (i & 1) + lane / 32) -- dma_src's maps, with the piece index split into parity (per lane) and pair (scalar).
-  constexpr bool BUFDMA = DEFER || (DBG & 32768) != 0;     // (DBG & 32768 alone: measurement build, the round-5 boundary on the buffer path)
-  uint32_t voA[2] = {0, 0}, voB[2] = {0, 0};
-  uint32_t soA = 0, soA2 = 0, soB = 0, soB2 = 0;
-  const rsrc4 rsA = operand_rsrc(p.A, (uint64_t)(A_T ? p.K : p.M) * (uint64_t)p.lda * 2);
-  const rsrc4 rsB = operand_rsrc(p.B, (uint64_t)(B_T ? p.K : p.N) * (uint64_t)p.ldb * 2);
-  auto buf_offsets = [&](auto trans_c, int64_t ld, int64_t row0, int64_t k0, uint32_t (&vo)[2], uint32_t& so, uint32_t& so2) {
-    constexpr bool TR = decltype(trans_c)::value;
-    int lane_o = lane;
-    asm volatile("" : "+v"(lane_o));          // (per segment, not hoisted: these are ~10 VALU)
-    const uint32_t ldb2 = (uint32_t)(ld * 2);
-    if constexpr (!TR) {
-      const uint32_t r = (uint32_t)(wave * 32 + (lane_o >> 3)), sl = (uint32_t)(lane_o & 7), sw = (uint32_t)(lane_o >> 4);
-      vo[0] = r * ldb2 + ((sl ^ sw) << 4);
-      vo[1] = (r + 8) * ldb2 + ((sl ^ (sw + 4)) << 4);
-      so = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((row0 * ld + k0) * 2));
-      so2 = so + 16 * ldb2;
-    } else {
-      const uint32_t k = (uint32_t)(wave * 8 + (lane_o >> 5)), sl = (uint32_t)(lane_o & 31), h = (uint32_t)(lane_o >> 5);
-      vo[0] = k * ldb2 + ((sl ^ (4 * h)) << 4);
-      vo[1] = (k + 2) * ldb2 + ((sl ^ (4 * (2 + h))) << 4);
-      so = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((k0 * ld + row0) * 2));
-      so2 = so + 4 * ldb2;
-    }
-  };
   auto openA = [&](int it) {
     Seg w;
     liveA = seg_cached(it, w);
     if (!liveA) return;
     nkA = w.ns; ktA = 0; tvA = tail_steps(w);
-    if constexpr (BUFDMA) { buf_offsets(std::integral_constant<bool, A_T>{}, p.lda, w.m0, w.k_begin, voA, soA, soA2); return; }
-    if constexpr (LEAN) kbA = reinterpret_cast<const char*>(p.A);
+    kbA = reinterpret_cast<const char*>(p.A);
 #pragma unroll
     for (int i = 0; i < CPW; ++i)
       srcA[i] = (uint32_t)(reinterpret_cast<const char*>(dma_src<A_T, BM, BKS>(p.A, p.lda, w.m0, p.M, w.k_begin, wave * CPW + i, lane)) -
@@ -277,15 +239,13 @@ void gemm_phase_kernel(GemmKArgs p) {
     liveB = seg_cached(it, w);
     if (!liveB) return;
     nkB = w.ns; ktB = 0; tvB = tail_steps(w);
-    if constexpr (BUFDMA) { buf_offsets(std::integral_constant<bool, B_T>{}, p.ldb, w.n0, w.k_begin, voB, soB, soB2); return; }
-    if constexpr (LEAN) kbB = reinterpret_cast<const char*>(p.B);
+    kbB = reinterpret_cast<const char*>(p.B);
 #pragma unroll
     for (int i = 0; i < CPW; ++i)
       srcB[i] = (uint32_t)(reinterpret_cast<const char*>(dma_src<B_T, BN, BKS>(p.B, p.ldb, w.n0, p.N, w.k_begin, wave * CPW + i, lane)) -
                            reinterpret_cast<const char*>(p.B));
   };
-  // one DMA piece (i = 0..3) of the next A / B image; *_done advances the cursor after the 4th (the placement table decides
-  // where in the K-tile each piece goes).
+  // one DMA piece (i = 0..3) of the next A / B image; done* advances the cursor after the 4th.
   // partial last K-tile (TAIL): piece c = 4 wave + i of a k-major image holds k rows 2 c and 2 c + 1 of the tile (lanes 0-31 /
   // 32-63, dma_src); a row at or past 16 tail_steps lies outside the operand: read the tile's row 0 in its place
   auto tail_back = [&](int i, int tv, int64_t ld) -> uint32_t {
@@ -294,42 +254,27 @@ void gemm_phase_kernel(GemmKArgs p) {
   };
   auto pieceA = [&](auto ic) {
     constexpr int i = decltype(ic)::value;
-    if constexpr (BUFDMA) { glds16b_lean<i * 1024>(rsA, voA[i & 1], (i >> 1) ? soA2 : soA, m0A); return; }
     uint32_t off = srcA[i];
     if constexpr (TAIL) { if (tvA < 4 && ktA == nkA - 1) off -= tail_back(i, tvA, p.lda); }
-    if constexpr (LEAN) {
-      glds16s_lean<i * 1024, EPI == EPI_GEN ? 3 : 0>(kbA, off, m0A);
-    } else {
-      const uint32_t dst = smem_base + (uint32_t)(nA * PCfg::A_BYTES + wave * (CPW * 1024) + i * 1024);
-      glds16s(p.A, off, __builtin_amdgcn_readfirstlane(dst));
-      srcA[i] += stepA;
-    }
+    glds16s_lean<i * 1024, EPI == EPI_GEN ? 3 : 0>(kbA, off, m0A);
   };
   auto doneA = [&]() {
     nA = nA == PCfg::NA - 1 ? 0 : nA + 1;
-    if constexpr (BUFDMA) { soA += stepA; soA2 += stepA; }
-    if constexpr (LEAN) { kbA += stepA; m0A = nA == 0 ? m0A - (uint32_t)((PCfg::NA - 1) * PCfg::A_BYTES) : m0A + (uint32_t)PCfg::A_BYTES; }
+    kbA += stepA; m0A = nA == 0 ? m0A - (uint32_t)((PCfg::NA - 1) * PCfg::A_BYTES) : m0A + (uint32_t)PCfg::A_BYTES;
     if (++ktA == nkA) openA(++itA);
   };
   auto pieceB = [&](auto ic) {
     constexpr int i = decltype(ic)::value;
-    if constexpr (BUFDMA) { glds16b_lean<i * 1024>(rsB, voB[i & 1], (i >> 1) ? soB2 : soB, m0B); return; }
     uint32_t off = srcB[i];
     if constexpr (TAIL) { if (tvB < 4 && ktB == nkB - 1) off -= tail_back(i, tvB, p.ldb); }
-    if constexpr (LEAN) {
-      glds16s_lean<i * 1024, EPI == EPI_GEN ? 3 : 0>(kbB, off, m0B);
-    } else {
-      const uint32_t dst = smem_base + (uint32_t)(PCfg::B_BASE + (nB & 1) * PCfg::B_BYTES + wave * (CPW * 1024) + i * 1024);
-      glds16s(p.B, off, __builtin_amdgcn_readfirstlane(dst));
-      srcB[i] += stepB;
-    }
+    glds16s_lean<i * 1024, EPI == EPI_GEN ? 3 : 0>(kbB, off, m0B);
   };
   auto doneB = [&]() {
     ++nB;
-    if constexpr (BUFDMA) { soB += stepB; soB2 += stepB; }
-    if constexpr (LEAN) { kbB += stepB; m0B = (nB & 1) ? m0B + (uint32_t)PCfg::B_BYTES : m0B - (uint32_t)PCfg::B_BYTES; }
+    kbB += stepB; m0B = (nB & 1) ? m0B + (uint32_t)PCfg::B_BYTES : m0B - (uint32_t)PCfg::B_BYTES;
     if (++ktB == nkB) openB(++itB);
   };
+  // prologue: the four pieces of the next A / B image, if the cursor is live
   auto issueA = [&]() -> bool {
     if (!liveA) return false;
     static_for<CPW>([&](auto ic) { pieceA(ic); });
@@ -343,21 +288,27 @@ void gemm_phase_kernel(GemmKArgs p) {
     return true;
   };
 
-  // the pieces the placement table puts into slot SLOT (ia / ib: the cursors were live when the segment that owns them began)
-  auto emit = [&](auto slot_c, auto ia, auto ib) {      // ia / ib: bool, or std::true_type in the all-live loop body
-    constexpr int SLOT = decltype(slot_c)::value;
-    constexpr PiecePlace pp = piece_place(PL);
-    if (DBG & 4) return;
+  // K loop: the same for operand A (b_c = std::false_type) or B (std::true_type), fenced so that the scheduler leaves the pieces at
+  // the head of their segment; live = the cursor was live when the segment began (bool, or std::true_type in the all-live loop
+  // body).  (One lambda for both operands and one liveness test per piece: this is the shape hipcc's inliner was tuned on -- with a
+  // lambda per operand, or the prologue's form, it inlines the segment decode behind doneA / doneB differently and every phase
+  // kernel's code changes.)
+  auto emit = [&](auto b_c, auto live) {
+    constexpr bool OPB = decltype(b_c)::value;
+    __builtin_amdgcn_sched_barrier(0);
     static_for<4>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
-      if constexpr (pp.slot[i] == SLOT) { if (ia) { pieceA(ic); if (i == 3) doneA(); } }
+      if constexpr (!OPB) { if (live) { pieceA(ic); if (i == 3) doneA(); } }
     });
     static_for<4>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
-      if constexpr (pp.slot[4 + i] == SLOT) { if (ib) { pieceB(ic); if (i == 3) doneB(); } }
+      if constexpr (OPB) { if (live) { pieceB(ic); if (i == 3) doneB(); } }
     });
+    __builtin_amdgcn_sched_barrier(0);
   };
-#define DVLA_SLOT(N, IA, IB) do { __builtin_amdgcn_sched_barrier(0); emit(std::integral_constant<int, N>{}, IA, IB); __builtin_amdgcn_sched_barrier(0); } while (0)
+  // Two bare scheduling barriers: where other placements used to issue pieces (behind the fragment reads, behind their wait).
+  // Nothing is issued there now, but hipcc schedules several product kernels differently without the pair.
+#define DVLA_SCHED_FENCE2() do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_sched_barrier(0); } while (0)
 
   // ---- prologue: A(0), B(0), A(1), B(1) in this order; the first two must have landed before the first fragment read ----
   openA(0); openB(0);
@@ -368,21 +319,21 @@ void gemm_phase_kernel(GemmKArgs p) {
   if (a1 && b1) wait_vmcnt<2 * CPW>(); else wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
 
-  // DBG & 64: waves 0 and 4 of workgroup 0 record s_memtime at the eight segment edges of their first 32 K-tiles into
+  // STAMPS: waves 0 and 4 of workgroup 0 record s_memtime at the eight segment edges of their first 32 K-tiles into
   // p.workspace (as uint64[2][32][8]) -- the timeline the schedule is tuned against (tests/probes/gemm_probe.cpp --stamps)
   uint64_t* stamps = nullptr;
-  if constexpr ((DBG & 64) != 0) {
+  if constexpr (STAMPS) {
     if (blockIdx.x == 0 && (wave == 0 || wave == 4) && p.workspace) stamps = reinterpret_cast<uint64_t*>(p.workspace) + (wave >> 2) * 256;
   }
   auto stamp = [&](int kt_global, int e) {
-    if constexpr ((DBG & 64) != 0) {
+    if constexpr (STAMPS) {
       if (stamps && kt_global < 32 && lane == 0) stamps[kt_global * 8 + e] = __builtin_amdgcn_s_memtime();
     }
   };
   // tile-boundary stamps (uint64[2][16][4] behind the K-tile stamps): 0 = K loop left, 1 = groups re-aligned, 2 = epilogue
   // code done (all stores issued), 3 = the next tile's K loop entered
   auto stamp_tile = [&](int tile, int e) {
-    if constexpr ((DBG & 64) != 0) {
+    if constexpr (STAMPS) {
       if (stamps && tile < 16 && lane == 0)
         (reinterpret_cast<uint64_t*>(p.workspace) + 512 + (wave >> 2) * 64)[tile * 4 + e] = __builtin_amdgcn_s_memtime();
     }
@@ -399,25 +350,13 @@ void gemm_phase_kernel(GemmKArgs p) {
   // so the sum of a tile row (column) is SPREAD over up to four of its tiles: tile column c < S = min(4, tiles_n) sums the K-tiles
   // with kt % S == c into its own KSUM_PARTS partial rows (p.ksum_parts = 8 S rows per K slice; the reduction adds them up) -- with
   // only the first tile column summing, the dots cost a launch 7-13 % (profiles/r05_gemm_ksum_probe.txt).
-  // The summing code exists only in the builds the dispatcher launches when a k-sum is asked for (DBG & 8192; the TT layout = the
+  // The summing code exists only in the builds the dispatcher launches when a k-sum is asked for (PHASE_KSUM; the TT layout = the
   // weight gradients): a launch without k-sums runs the identical kernel without the four accumulators and their flags.
-  constexpr bool KSUM = EPI == EPI_F32 && (DBG & 8192) != 0;
+  constexpr bool KSUM = EPI == EPI_F32 && (FEAT & PHASE_KSUM) != 0;
   // (Round 5, measured and not kept: no s_setprio at all -0.5 ... +1 %, static priority 1 for group 1 without per-segment flips
   // -1 ... -3 %; the groups keeping their one-segment skew through the tile boundary -- group 0's epilogue beside group 1's last
-  // multiply segment -- -1 ... -2 %: profiles/r05_gemm_placement_probe*.txt, variants 55 / 56 / 71 / 72.)
+  // multiply segment -- -1 ... -2 %: profiles/r05_gemm_placement_probe*.txt.)
   int u = 0, ua = 0;   // global K-tile counter of the multiply, and u % 3
-  f32x16 acc_carried[DEFER ? 2 : 1][DEFER ? 4 : 1];      // DEFER: the accumulators live across tile boundaries
-  if constexpr (DEFER) {     // (defined once: the first K-tile of every segment overwrites them)
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc_carried[i][j][r] = 0.f;
-  }
-  bool pend = false;          // DEFER: slabs 1-3 of the previous tile (origin pm0, pn0) are still in the accumulators
-  int pm0 = 0, pn0 = 0;
-  bool aligned_now = true;    // the two groups are at the same program point (false: group 1 runs one segment behind)
   for (int it = 0;; ++it) {
     // The segment's tile origin / split / kind stay live across the K loop as SCALARS (6 SGPRs, spilled to VGPR lanes when
     // the allocator runs out: one v_readlane each) -- re-deriving them for the epilogue was ~150 dependent scalar instructions
@@ -430,11 +369,9 @@ void gemm_phase_kernel(GemmKArgs p) {
     const int seg_ns = w.ns;
     const int seg_tv = __builtin_amdgcn_readfirstlane(tail_steps(w));
 
-    // per tile (dead at the tile top -- with two copies of the K loop anything else costs a register shuffle through scratch); zeroed
-    // here, or (ZC) left undefined: the first K-tile's multiplies take a literal-zero C operand
-    f32x16 acc_tile[DEFER ? 1 : 2][DEFER ? 1 : 4];
-    f32x16 (&acc)[2][4] = *[&]() { if constexpr (DEFER) return &acc_carried; else return &acc_tile; }();
-    if constexpr (!ZC) {
+    // per tile (dead at the tile top -- with two copies of the K loop anything else costs a register shuffle through scratch)
+    f32x16 acc[2][4];
+    {
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -442,46 +379,26 @@ void gemm_phase_kernel(GemmKArgs p) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     }
-    // DEFER: is this tile's epilogue deferred (a whole tile with a successor); the bias of the wave's 64 columns (lane l: column
-    // n0 + 64 wc + l) is requested in LOAD2 of the tile's LAST K-tile and added behind the K loop -- a register that crossed the
-    // in-loop epilogue of the previous tile tipped hipcc's allocator into spilling the DMA offsets (171 spills for ONE register)
     Seg nx;
-    bool has_next = false, defer_this = false, tile_bias = false;
-    uint32_t braw = 0;
-    int bias_young = 0;       // DMA pieces issued behind the bias load
-    if constexpr (DEFER) {
-      has_next = seg_cached(it + 1, nx);
-      defer_this = w.kind == 0 && has_next;
-      tile_bias = p.bias != nullptr && w.kind != 2;      // (a stream-K tail's partial sums are added to the owner's, which carry it)
-    }
-    const bool fresh = DEFER ? aligned_now : true;      // this tile starts behind an old-style boundary (or is the first)
-
     float ksa[4] = {0.f, 0.f, 0.f, 0.f};     // k-sums of this wave's A row blocks (a-lo 0, 1; a-hi 2, 3) -- or, [0] and [1], of its B column blocks (a launch sums one operand)
     // S = p.ksum_parts / KSUM_PARTS tiles of a row (column) share its sum; this tile's column (row) index c takes the K-tiles with
     // kt % S == c: ks_cnt counts down to its next K-tile (-1: this tile does not sum).  Two live scalars.
     const int ks_c = !KSUM ? 0 : p.ksum_op == 1 ? w.n0 / BN : w.m0 / BM;
     int ks_cnt = (KSUM && ks_c * KSUM_PARTS < p.ksum_parts) ? ks_c : -1;
-    if (grp == 1 && fresh) __builtin_amdgcn_s_barrier();   // stagger: group 1 runs one segment behind group 0
-    aligned_now = false;
+    if (grp == 1) __builtin_amdgcn_s_barrier();   // stagger: group 1 runs one segment behind group 0
     __builtin_amdgcn_sched_barrier(0);
     if (it > 0) stamp_tile(it - 1, 3);
 
     // the K loop of one output tile; live_c = std::true_type: both DMA cursors stay live for the whole tile, every liveness test
     // folds away.  The cursors run two K-tiles ahead of the multiply, so that holds whenever a next work segment of at least two
-    // K-tiles exists: the LEAN build runs this copy for every tile but the workgroup's last.
+    // K-tiles exists: this copy runs for every tile but the workgroup's last.
     auto kloop = [&](auto live_c) {
     for (int kt = 0; kt < seg_ns; ++kt, ++u, ua = (ua == PCfg::NA - 1 ? 0 : ua + 1)) {
       const char* bufA = smem + ua * PCfg::A_BYTES;                         // ua = u % 3
       const char* bufB = smem + PCfg::B_BASE + (u & 1) * PCfg::B_BYTES;
       bf16x8 fa[2][4], fb[2][4];   // [sub-tile][k16-step]
-      if (DBG & 2) {
-#pragma unroll
-        for (int x = 0; x < 2; ++x)
-#pragma unroll
-          for (int y = 0; y < 4; ++y) { fa[x][y] = bf16x8{1, 2, 3, 4, 5, 6, 7, (short)lane}; fb[x][y] = bf16x8{1, 2, 3, 4, 5, 6, 7, (short)kt}; }
-      }
 
-      // (DMA piece placement: piece_place() at the top of the file.  Both operands run TWO tiles ahead -- A(u+2) and B(u+2) are
+      // (DMA piece placement: the top of the file.  Both operands run TWO tiles ahead -- A(u+2) and B(u+2) are
       // issued during tile u; three A images make that possible -- so the counted waits below name pieces issued a whole tile
       // earlier and do not stall.)
       // The first K-tile behind an epilogue waits for NOTHING (round 5).  vmcnt is one in-order counter for loads and stores: a
@@ -491,47 +408,21 @@ void gemm_phase_kernel(GemmKArgs p) {
       // (vmcnt(0) below: the youngest is half a K-tile old) and K-tile 0 of the next tile skips both of its waits; K-tile 1's
       // wait then meets stores that have had a whole K-tile to drain.
       // (Not in the partial-K-tile build: its K ranges are 80+ K-tiles long, and one more live scalar tips its loop into spilling.)
-      const bool after_epi = LEAN && !TAIL && kt == 0 && it > 0 && fresh;
+      const bool after_epi = !TAIL && kt == 0 && it > 0;
       const bool first = kt == 0;
-      // (DEFER: the lane-dependent parts of the fragment addresses are re-derived per K-tile -- ~10 VALU in a load segment --
-      //  instead of living in four registers across the in-loop epilogue, where hipcc spilled them and reloaded them behind vmcnt(0))
-      int lane_k = lane;
-      if constexpr (DEFER && (DBG & 65536) == 0) asm volatile("" : "+v"(lane_k));
-      int nst = 0;      // DEFER: epilogue stores this wave has issued in this K-tile so far (the counted waits skip them)
+      int lane_k = lane;      // (a copy: with `lane` itself hipcc swaps the operands of one address instruction)
       // ---------------- LOAD1 ----------------
       stamp(u, 0);
       const auto ia = live_or(live_c, liveA);
-      DVLA_SLOT(0, ia, false);
-      if constexpr (DEFER) {
-        // the previous tile's epilogue: its accumulators are complete, every fragment register is dead, the partner group multiplies
-        if (first && pend && pn0 + wc * 64 < p.N) {
-          int lane_e = lane;
-          asm volatile("" : "+v"(lane_e));
-          if constexpr ((DBG & 131072) != 0) __builtin_amdgcn_s_setprio(2);      // (measurement: the epilogue above the partner's multiply segment)
-          if constexpr ((DBG & 64) != 0) {      // slab stamps of the in-loop epilogue (same slots as the boundary epilogue's)
-            auto st = [&](int idx) {
-              __builtin_amdgcn_sched_barrier(0);
-              if (stamps && it == 2 && lane == 0)
-                (reinterpret_cast<uint64_t*>(p.workspace) + 640 + (wave >> 2) * 16)[idx] = __builtin_amdgcn_s_memtime();
-              __builtin_amdgcn_sched_barrier(0);
-            };
-            reg_epilogue<4, EPI, decltype(st), true>(p, acc, lane_e, (int64_t)pm0 + grp * 128, (int64_t)pn0 + wc * 64, 0, st);
-          } else {
-            reg_epilogue<4, EPI, NoStamp, true>(p, acc, lane_e, (int64_t)pm0 + grp * 128, (int64_t)pn0 + wc * 64, 0);
-          }
-          nst = p.preact ? 32 : 16;
-          if constexpr ((DBG & 131072) != 0) __builtin_amdgcn_s_setprio(0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      emit(std::false_type{}, ia);
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) if (!(DBG & 2)) fb[i][ks] = ring_frag<B_T, BN, BKS>(bufB, wc * 64 + i * 32, ks, lane_k);
+        for (int i = 0; i < 2; ++i) fb[i][ks] = ring_frag<B_T, BN, BKS>(bufB, wc * 64 + i * 32, ks, lane_k);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) if (!(DBG & 2)) fa[j][ks] = ring_frag<A_T, BM, BKS>(bufA, grp * 128 + j * 32, ks, lane_k);
+        for (int j = 0; j < 2; ++j) fa[j][ks] = ring_frag<A_T, BM, BKS>(bufA, grp * 128 + j * 32, ks, lane_k);
       }
-      DVLA_SLOT(1, ia, false);
+      DVLA_SCHED_FENCE2();
       wait_lds();
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (TAIL) {      // the dead k16-steps of a partial last K-tile contribute nothing (fragment reads have retired)
@@ -558,16 +449,21 @@ void gemm_phase_kernel(GemmKArgs p) {
         }
         __builtin_amdgcn_sched_barrier(0);
       }
-      DVLA_SLOT(2, ia, false);
+      DVLA_SCHED_FENCE2();
       stamp(u, 1);
-      if (!(DBG & 8)) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
       stamp(u, 2);
       // ---------------- MFMA1 ----------------
       __builtin_amdgcn_s_setprio(1);
       static_for<4>([&](auto ksc) {
         constexpr int ks = decltype(ksc)::value;
+        // NOTE on the two never-taken statements of this lambda and of MFMA2's (ZC is false; the placement has no piece in a multiply
+        // segment): they are what is left of the deferred epilogue's zero-C multiply and of the other placements.  They generate no
+        // code, but they make the lambda capture `first`, `emit`, `ia` (`ib`), and without them hipcc orders three scalar copies
+        // of the k-sum kernel (PHASE_KSUM) differently.  Kept so that this cleanup leaves every product kernel byte-identical;
+        // delete them together with the next change that alters that kernel's code anyway.
         if constexpr (ZC && ks == 0) {
-          if (first) {        // a segment's first K-tile: C = 0 (nothing to zero)
+          if (first) {
             const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -584,39 +480,28 @@ void gemm_phase_kernel(GemmKArgs p) {
         for (int i = 0; i < 2; ++i)
 #pragma unroll
           for (int j = 0; j < 2; ++j)
-            if (!(DBG & 1)) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[i][ks], fa[j][ks], acc[i][j], 0, 0, 0);
-            else asm volatile("" :: "v"(fb[i][ks]), "v"(fa[j][ks]));
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[i][ks], fa[j][ks], acc[i][j], 0, 0, 0);
         }
-        if constexpr (pieces_up_to(PL, 3 + ks) != pieces_up_to(PL, 2 + ks)) DVLA_SLOT(3 + ks, ia, false);
+        if constexpr (pieces_up_to(PL, 3 + ks) != pieces_up_to(PL, 2 + ks)) emit(std::false_type{}, ia);
       });
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
       stamp(u, 3);
-      if (!(DBG & 8)) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
       stamp(u, 4);
       // ---------------- LOAD2 ----------------
       const auto ib = live_or(live_c, liveB);
-      if constexpr (DEFER) {
-        if (kt == seg_ns - 1 && tile_bias) {      // the tile's bias: in flight during its last multiply segment (older than this K-tile's B pieces)
-          const int nb = w.n0 + wc * 64;
-          const uint32_t col = (uint32_t)((nb < p.N ? nb : 0) + lane_k);
-          braw = p.bias_f32 ? aload_b32(p.bias, 4 * col) : aload_u16(p.bias, 2 * col);
-          bias_young = ib ? CPW : 0;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      DVLA_SLOT(7, ia, ib);
+      emit(std::true_type{}, ib);
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) if (!(DBG & 2)) fa[j][ks] = ring_frag<A_T, BM, BKS>(bufA, grp * 128 + 64 + j * 32, ks, lane_k);
-      DVLA_SLOT(8, ia, ib);
+        for (int j = 0; j < 2; ++j) fa[j][ks] = ring_frag<A_T, BM, BKS>(bufA, grp * 128 + 64 + j * 32, ks, lane_k);
+      DVLA_SCHED_FENCE2();
       // group 1 sits one segment behind group 0, which reads tile u+1 in the next slot: group 1's pieces of A(u+1) / B(u+1)
       // (issued during ITS tile u-1) must have landed by now.  Younger than those: the pieces of this tile issued so far
-      // (and, DEFER, the slab stores of this K-tile).
+      // (pieces_up_to: all eight).
       if (grp == 1 && !after_epi) {
-        if (DEFER && nst != 0) { if (ia && ib) wait_vmcnt_dyn(pieces_up_to(PL, 8) + nst); else wait_vmcnt<0>(); }
-        else { if (ia && ib) wait_vmcnt<pieces_up_to(PL, 8)>(); else wait_vmcnt<0>(); }
+        if (ia && ib) wait_vmcnt<pieces_up_to(PL, 8)>(); else wait_vmcnt<0>();
       }
       wait_lds();
       __builtin_amdgcn_sched_barrier(0);
@@ -638,9 +523,9 @@ void gemm_phase_kernel(GemmKArgs p) {
         ks_cnt = ks_cnt > 0 ? ks_cnt - 1 : (ks_cnt == 0 ? p.ksum_parts / KSUM_PARTS - 1 : ks_cnt);
         __builtin_amdgcn_sched_barrier(0);
       }
-      DVLA_SLOT(9, ia, ib);
+      DVLA_SCHED_FENCE2();
       stamp(u, 5);
-      if (!(DBG & 8)) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
       stamp(u, 6);
       // ---------------- MFMA2 ----------------
       __builtin_amdgcn_s_setprio(1);
@@ -664,32 +549,23 @@ void gemm_phase_kernel(GemmKArgs p) {
         for (int i = 0; i < 2; ++i)
 #pragma unroll
           for (int j = 0; j < 2; ++j)
-            if (!(DBG & 1)) acc[i][2 + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[i][ks], fa[j][ks], acc[i][2 + j], 0, 0, 0);
-            else asm volatile("" :: "v"(fb[i][ks]), "v"(fa[j][ks]));
+            acc[i][2 + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[i][ks], fa[j][ks], acc[i][2 + j], 0, 0, 0);
         }
-        if constexpr (pieces_up_to(PL, 10 + ks) != pieces_up_to(PL, 9 + ks)) DVLA_SLOT(10 + ks, ia, ib);
+        if constexpr (pieces_up_to(PL, 10 + ks) != pieces_up_to(PL, 9 + ks)) { emit(std::false_type{}, ia); emit(std::true_type{}, ib); }
       });
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
-      // everything but this tile's eight pieces (A(u+2), B(u+2)) -- and, DEFER, its slab stores -- has landed: A(u+1), B(u+1)
+      // everything but this tile's eight pieces (A(u+2), B(u+2)) has landed: A(u+1), B(u+1)
       if (!after_epi) {
-        if (DEFER && nst != 0) { if (ia && ib) wait_vmcnt_dyn(2 * CPW + nst); else wait_vmcnt<0>(); }
-        else { if (ia && ib) wait_vmcnt<2 * CPW>(); else wait_vmcnt<0>(); }
+        if (ia && ib) wait_vmcnt<2 * CPW>(); else wait_vmcnt<0>();
       }
-      if constexpr (DEFER) { if (first) pend = false; }
       stamp(u, 7);
-      if (!(DBG & 8)) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
         }
     };
-    if constexpr (LEAN && !(TAIL && KSUM)) {      // (the partial-K-tile + k-sum build keeps one copy of its loop: registers)
-      if constexpr (DEFER) {
-        // ONE copy of the loop: the accumulators now live across tile boundaries, and two loops that hold them in different
-        // registers cost a shuffle through scratch at every tile top (hipcc spilled 491 VGPRs)
-        kloop(std::false_type{});
-      } else {
-        const bool all_live = seg_cached(it + 1, nx) && nx.ns >= 2;
-        if (all_live) kloop(std::true_type{}); else kloop(std::false_type{});
-      }
+    if constexpr (!(TAIL && KSUM)) {      // (the partial-K-tile + k-sum build keeps one copy of its loop: registers)
+      const bool all_live = seg_cached(it + 1, nx) && nx.ns >= 2;
+      if (all_live) kloop(std::true_type{}); else kloop(std::false_type{});
     } else {
       kloop(std::false_type{});
     }
@@ -699,55 +575,15 @@ void gemm_phase_kernel(GemmKArgs p) {
       if (ks_cnt >= 0 && p.ksum_op == 1) ksum_store<4, 4>(p, ksa, lane, w.split, wc, 4, (int64_t)w.m0 + grp * 128, p.M, tc * KSUM_PARTS);
       if (ks_cnt >= 0 && p.ksum_op == 2) ksum_store<2, 4>(p, ksa, lane, w.split, grp, 2, (int64_t)w.n0 + wc * 64, p.N, tc * KSUM_PARTS);
     }
-    if constexpr (DEFER) {
-      if (tile_bias) {
-        // the bias as one short MFMA per accumulator block (gemm_impl.h bias_split): group 0 issues them beside group 1's last
-        // multiply segment, group 1 beside group 0's first of the next tile -- in front of an epilogue that outlasts either anyway
-        wait_vmcnt_dyn(bias_young);
-        uint32_t b_lo = braw, b_hi = braw;
-        settle(b_lo, b_hi);
-        if (!p.bias_f32) { b_lo <<= 16; b_hi <<= 16; }
-        swap_halves(b_lo, b_hi);            // b_hi: lanes 0-31 now hold what lanes 32-63 loaded (columns 32-63)
-        const bool lower = lane < 32;
-        const bf16x4v bfr0 = bias_split(__uint_as_float(b_lo), lower), bfr1 = bias_split(__uint_as_float(b_hi), lower);
-        const bf16x4v ones = bias_ones(lower);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x8bf16_1k(bfr0, ones, acc[0][j], 0, 0, 0);
-          acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x8bf16_1k(bfr1, ones, acc[1][j], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if (defer_this) { pend = true; pm0 = w.m0; pn0 = w.n0; continue; }   // slabs 1-3 ride in the next tile's first K-tile; the groups stay skewed
-    }
     stamp_tile(it, 0);
-    if constexpr (LEAN && !TAIL) wait_vmcnt<0>();   // every DMA piece has landed before the first store is issued (see after_epi)
+    if constexpr (!TAIL) wait_vmcnt<0>();   // every DMA piece has landed before the first store is issued (see after_epi)
     if (grp == 0) __builtin_amdgcn_s_barrier();   // re-align: both groups run the epilogue together
-    aligned_now = true;
     __builtin_amdgcn_sched_barrier(0);
     stamp_tile(it, 1);
     int lane_e = lane;
     asm volatile("" : "+v"(lane_e));              // (the per-lane epilogue addresses the compiler would hoist out of the segment
                                                   //  loop and spill are re-derived per tile from lane_e)
-    if (DBG & 16) {        // no epilogue at all (keep the accumulators alive)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) asm volatile("" :: "v"(acc[i][j]));
-    } else if (DBG & 32) { // stores only: 16 x 16 B per lane straight from accumulator registers (no conversion, no exchange)
-      const int l31 = lane_e & 31, g = lane_e >> 5;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int64_t m = w.m0 + grp * 128 + j * 32 + l31;
-        if (m < p.M) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-            *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.C) + m * p.ldc + w.n0 + wc * 64 + 16 * q + 8 * g) =
-                make_uint4(__float_as_uint(acc[q >> 1][j][4 * (q & 1)]), __float_as_uint(acc[q >> 1][j][4 * (q & 1) + 1]),
-                           __float_as_uint(acc[q >> 1][j][4 * (q & 1) + 2]), __float_as_uint(acc[q >> 1][j][4 * (q & 1) + 3]));
-        }
-      }
-    } else if (w.kind == 2) {
+    if (w.kind == 2) {
       // stream-K tail: the 128 accumulators of every lane -> slab `perm`, quad (i, j, rq) of wave `wave` at
       // [(wave * 32 + quad) * 64 + lane] (16 B per lane, 1 KiB per instruction), write-through (sc1: the owner sits on
       // another XCD); then every wave drains its stores, the workgroup meets, and one lane raises the flag.
@@ -790,7 +626,7 @@ void gemm_phase_kernel(GemmKArgs p) {
             }
         }
       }
-      if constexpr ((DBG & 64) != 0) {
+      if constexpr (STAMPS) {
         // slab stamps of tile 1 (uint64[2][16] behind the boundary stamps): 0 = entry, 1 + 2j = slab j converted and transposed,
         // 2 + 2j = slab j's stores issued
         auto st = [&](int idx) {
@@ -799,20 +635,20 @@ void gemm_phase_kernel(GemmKArgs p) {
             (reinterpret_cast<uint64_t*>(p.workspace) + 640 + (wave >> 2) * 16)[idx] = __builtin_amdgcn_s_memtime();
           __builtin_amdgcn_sched_barrier(0);
         };
-        reg_epilogue<4, EPI, decltype(st), DEFER>(p, acc, lane_e, w.m0 + grp * 128, w.n0 + wc * 64, w.split, st);
+        reg_epilogue<4, EPI, decltype(st)>(p, acc, lane_e, w.m0 + grp * 128, w.n0 + wc * 64, w.split, st);
       } else {
-        reg_epilogue<4, EPI, NoStamp, DEFER>(p, acc, lane_e, w.m0 + grp * 128, w.n0 + wc * 64, w.split);
+        reg_epilogue<4, EPI>(p, acc, lane_e, w.m0 + grp * 128, w.n0 + wc * 64, w.split);
       }
     }
-    if constexpr ((DBG & 64) != 0) __builtin_amdgcn_sched_barrier(0);
+    if constexpr (STAMPS) __builtin_amdgcn_sched_barrier(0);
     stamp_tile(it, 2);
   }
 }
 
-template <bool A_T, bool B_T, int EPI, int DBG = 0>
+template <bool A_T, bool B_T, int EPI, int FEAT = 0>
 void launch_phase_one(const GemmKArgs& a, int split_k, hipStream_t stream) {
   static bool attr_set = false;
-  auto kern = &gemm_phase_kernel<A_T, B_T, EPI, DBG>;
+  auto kern = &gemm_phase_kernel<A_T, B_T, EPI, FEAT>;
   if (!attr_set) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, PCfg::SMEM_BYTES);
     attr_set = true;

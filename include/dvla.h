@@ -117,9 +117,9 @@ int dvla_gemm_bf16(const dvla_gemm_params* p, void* stream);
  * kernel (256x256, K-tile 64, two wave groups in ping-pong); 9 = the phase kernel under the stream-K hybrid schedule (whole
  * rounds one tile per CU; the last, partial rounds as equal K-iteration ranges per group of 16 CUs, the two halves of a
  * shared tile combined in-kernel through a 256-KiB fp32 slab); 11 = the few-rows kernel (M <= 512).  A configuration that does
- * not take a shape falls back
- * inside the library.  All differ only in fp32 summation order.  81..89 = ablation / timeline builds of the phase kernel
- * (wrong results by design, tests/probes/gemm_probe.cpp).
+ * not take a shape, and any number not named here, falls back to the register-staged kernel inside the library
+ * (dvla_last_gemm_variant() then reports 2).  All differ only in fp32 summation order.  89 = the timeline build of the phase
+ * kernel (s_memtime stamps into the workspace; only in a library built with DVLA_ABLATIONS=1, tests/probes/gemm_probe.cpp --stamps).
  * Stream-K scratch: 64 MiB + flags per (device, stream), hipMalloc'ed on the first launch that uses it (never while the
  * stream is being captured -- such launches take the plain schedule) and kept; DVLA_GEMM_STREAMK=0 turns the schedule off. */
 void dvla_set_gemm_variant(int variant);

@@ -149,6 +149,18 @@ def check_gemm_wide_stride(variant=7, M=300, N=256, K=128, stride=8_500_000):
     return out
 
 
+def check_gemm_retired_variant(variant, M=256, N=256, K=128):
+    """a forced variant number that names nothing -- 44 and 85 were measurement builds of the phase kernel (NN layout, plain
+    epilogue) until they were removed -- selects nothing but the fallback: right values from the register-staged kernel,
+    `dvla_last_gemm_variant() == 2`.  The shape is the smallest the phase kernel takes (one 256 x 256 tile, two K-tiles)."""
+    from dreamvla_amd._lib import load
+    out = check_gemm(M=M, N=N, K=K, variant=variant)
+    ran = int(load().dvla_last_gemm_variant())
+    out.append({"name": f"  ... retired variant {variant} ran the register-staged kernel (last variant {ran})", "rel_l2": 0.0, "tol": 0.0,
+                "ok": ran == 2})
+    return out
+
+
 # the whole-line epilogue of the ring / phase kernels addresses a wave's window of at most 128 rows (csrc/gemm_impl.h
 # EPI_WINDOW_ROWS) with 32-bit byte offsets: the smallest bf16 row stride, in whole 16-byte vectors, at which the window's last
 # row lies >= 4 GiB behind its first -- (128 - 1) * stride * 2 >= 2^32 -> 16 909 328 elements
@@ -1585,6 +1597,9 @@ def all_checks(quick=False):
     for v in (4, 7, 8):
         L += [(check_gemm_wide_stride_out, dict(variant=v, which="out")),
               (check_gemm_wide_stride_out, dict(variant=v, which="residual"))]
+    # forced variant numbers that name nothing (any more): the fallback, and nothing else, runs
+    for v in (44, 85):
+        L.append((check_gemm_retired_variant, dict(variant=v)))
     return L
 
 

@@ -3,6 +3,7 @@
 //   hipcc --offload-arch=gfx950 -O2 -std=c++17 tests/probes/gemm_probe.cpp -o build/gemm_probe -Ldreamvla_amd -ldvla_hip \
 //         -Wl,-rpath,'$ORIGIN/../dreamvla_amd'
 // Usage: gemm_probe [--variants 0,2,4,...] [--iters N] [--check-only] [--cases model|small|big]
+//        gemm_probe --stamps [K]      timeline of the phase kernel (variant 89); needs a library built with DVLA_ABLATIONS=1
 // For every case: a small-shape correctness pass of each variant against a naive fp32 device reference that restates the
 // epilogue of include/dvla.h (exact erf / tanh), then paired timing rounds (variants interleaved in one process, median
 // and min reported -- cdna guide section 5.4 rule 24).  One JSON object per line on stdout.
@@ -232,7 +233,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--cases") && i + 1 < argc) which = argv[++i];
     else if (!strcmp(argv[i], "--only") && i + 1 < argc) only = atoi(argv[++i]);     // run case number `only` of the group alone
   }
-  if (stamps) {   // timeline of the phase kernel (variants 89 / 97 / 98): s_memtime at the 8 segment edges of the first 32 K-tiles, waves 0 and 4
+  if (stamps) {   // timeline of the phase kernel (variant 89, DVLA_ABLATIONS=1 builds only): s_memtime at the 8 segment edges of the first 32 K-tiles, waves 0 and 4
     Case c{"stamps", 20832, 4096, stamps_k, 0, 0, "plain", 1};
     Problem q = make_problem(c, c.M);
     q.ws = dalloc((2 * 256 + 2 * 64 + 32) * 8); q.p.workspace = q.ws.p;
@@ -359,13 +360,6 @@ int main(int argc, char** argv) {
       {"K1024 NN", 20832, 4096, 1024, 0, 0, "plain", 1},
       {"K1024 NT", 20832, 4096, 1024, 0, 1, "plain", 1},
       {"K1024 NN fused", 20832, 4096, 1024, 0, 0, "gelu_tanh_preact", 1},
-    };
-  } else if (which == "nn") {    // the measurement variants 40..79 of the phase kernel take the NN layout with the plain epilogue only
-    cases = {
-      {"square NN", 8192, 8192, 8192, 0, 0, "plain", 1},
-      {"K1024 NN", 20832, 4096, 1024, 0, 0, "plain", 1},
-      {"K768 NN", 88256, 3072, 768, 0, 0, "plain", 1},
-      {"K4096 NN", 20832, 1024, 4096, 0, 0, "plain", 1},
     };
   } else if (which == "defer") {   // round 6: one case per (layout, P class, bias / pre-activation) of the deferred-epilogue builds
     cases = {

@@ -6,8 +6,13 @@ preceded by such a write and the hazard nop.
 
 Round 6 adds the VALU -> VMEM scalar hazard audit (test_no_asm_vmem_reads_a_freshly_reloaded_sgpr): hipcc reloads spilled SGPRs with
 v_readlane_b32 and pads the five wait states a VMEM instruction needs before it may read such a register -- but not for the
-instructions INSIDE an asm statement, which it cannot see.  The first deferred-epilogue build read its bias through a stale base
-register that way (memory faults in every erf-GELU launch).  tests/probes/asm_hazard_audit.py is the same check on a -save-temps file."""
+instructions INSIDE an asm statement, which it cannot see.  A measurement build of round 6 (the deferred epilogue, since removed)
+read its bias through a stale base register that way: memory faults in every erf-GELU launch.  tests/probes/asm_hazard_audit.py is
+the same check on a -save-temps file.
+
+Every phase and ring kernel of the library is audited: the measurement builds that saved and restored M0 (the round-4 issue code) or
+issued their pieces through a buffer descriptor are gone, and the one measurement build left (DVLA_ABLATIONS=1: the phase kernel's
+s_memtime stamps) issues its pieces exactly like the product kernels."""
 import os
 import re
 import subprocess
@@ -22,8 +27,8 @@ OBJDUMP = os.path.join(K.LLVM, "llvm-objdump")
 
 
 def _is_dma(t):
-    """an LDS-DMA instruction: global_load_lds_dwordx4, or (round 6, the measurement builds on the buffer-descriptor path) buffer_load_dwordx4 ... lds"""
-    return t.startswith("global_load_lds_dwordx4") or (t.startswith("buffer_load_dwordx4") and t.split()[-1] == "lds")
+    """an LDS-DMA instruction"""
+    return t.startswith("global_load_lds_dwordx4")
 
 
 def _functions(*needles):
@@ -56,14 +61,11 @@ def test_no_instruction_of_the_phase_kernels_reads_m0():
     fns = _functions("gemm_phase_kernel", "gemm_ring_kernel")
     n_phase = sum("gemm_phase_kernel" in n for n in fns)
     n_ring = sum("gemm_ring_kernel" in n for n in fns)
-    assert n_phase >= 33 and n_ring >= 96, (n_phase, n_ring)   # phase: 4 layouts x 8 classes + partial-K-tile build (+ measurement
-    lean = 0                                                    # variants); ring: 3 configurations x 4 layouts x 8 classes
+    assert n_phase >= 33 and n_ring >= 96, (n_phase, n_ring)   # phase: 4 layouts x 8 classes + partial-K-tile / k-sum builds (+ the
+    lean = 0                                                    # stamps build); ring: 3 configurations x 4 layouts x 8 classes
     for name, ins in fns.items():
         dma = [i for i, t in enumerate(ins) if _is_dma(t)]
         assert len(dma) >= (16 if "phase" in name else 4), (name, len(dma))  # phase: prologue 16 + 8 per copy of the K loop
-        legacy = any(re.match(r"s_mov_b32 s\d+, m0", t) for t in ins)      # the round-4 issue code saves and restores M0 (variants 40 / 41)
-        if legacy:
-            continue
         lean += 1
         for i, t in enumerate(ins):
             if "m0" not in re.split(r"\s+", t, 1)[-1] and not t.startswith("s_add_u32 m0") and not t.startswith("s_mov_b32 m0"):
@@ -75,7 +77,7 @@ def test_no_instruction_of_the_phase_kernels_reads_m0():
         for i in dma:                                                                   # every DMA: M0 write, hazard nop, DMA
             assert ins[i - 1].startswith("s_nop") and (ins[i - 2].startswith("s_add_u32 m0") or ins[i - 2].startswith("s_mov_b32 m0")), \
                 (name, ins[i - 3:i + 1])
-    assert lean >= 33 + 96, lean
+    assert lean == len(fns) and lean >= 33 + 96, (lean, len(fns))
 
 
 ATTN_DMA = ("attn_fwd_ring_kernel", "attn_bwd_dq_ring_kernel", "attn_bwd_dkv_ring_kernel", "attn_fwd_short_kernel", "attn_bwd_short_kernel")
@@ -88,7 +90,8 @@ def test_no_instruction_of_the_attention_dma_kernels_reads_m0():
     assert all(any(k in n for n in fns) for k in ATTN_DMA), sorted(fns)
     for name, ins in fns.items():
         dma = [i for i, t in enumerate(ins) if t.startswith("global_load_lds_dwordx4")]
-        assert len(dma) >= 2, (name, len(dma))
+        if not ("attn_fwd_ring_kernel" in name and "ILi0E" not in name):     # (ablation builds of the forward ring kernel, DVLA_ABLATIONS=1:
+            assert len(dma) >= 2, (name, len(dma))                            #  some issue no DMA at all; the M0 rules below hold for them too)
         for t in ins:
             ops = re.split(r"\s+", t, 1)
             if len(ops) < 2 or "m0" not in ops[1]:
