@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("DVLA_LIB") or os.path.join(_HERE, "libdvla_hip.so")
 
 DT_BF16, DT_F32 = 0, 1
 CROP_OUT_U8, CROP_OUT_BF16 = 0, 1      # DVLA_CROP_OUT_* of include/dvla.h (dvla_image_resized_crop's out_kind)
-ABI_VERSION = 8          # DVLA_ABI_VERSION of include/dvla.h
+ABI_VERSION = 9          # DVLA_ABI_VERSION of include/dvla.h
 ACT = {"none": 0, "gelu": 1, "gelu_erf": 1, "gelu_tanh": 2, "gelu_new": 2, "relu": 3, "silu": 4,
        "quick_gelu": 5, "tanh": 6, "sigmoid": 7}
 
@@ -107,8 +107,6 @@ SYMBOLS = {
     "dvla_last_gemm_variant": (C.c_int, []),
     "dvla_set_gemm_schedule": (None, [C.c_int, C.c_int]),
     "dvla_get_gemm_schedule": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "dvla_layernorm_fwd": (C.c_int, [_P, _P, _P, _I32, _P, _P, _P, _I64, _I64, _F, _P]),
-    "dvla_layernorm_bwd": (C.c_int, [_P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _I64, _I64, _P]),
     "dvla_layernorm_bwd_add": (C.c_int, [_P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _I32, _P, _I64, _I64, _P]),
     "dvla_layernorm_bwd_partial_rows": (_I64, []),
     "dvla_layernorm_fwd_rows": (C.c_int, [_P, _P, _P, _I32, _P, _P, _P, _I64, _I64, _F, _I32, _I32, _I32, _I32, _P]),
@@ -119,7 +117,6 @@ SYMBOLS = {
     "dvla_attn_small_bwd": (C.c_int, [C.POINTER(AttnParams), _I32, _P]),
     "dvla_attn_hd_fwd": (C.c_int, [C.POINTER(AttnParams), _I32, _P]),
     "dvla_attn_hd_bwd": (C.c_int, [C.POINTER(AttnParams), _I32, _P]),
-    "dvla_colsum": (C.c_int, [_P, _I64, _I64, _I64, _P, _P, _P]),
     "dvla_colsum_dt": (C.c_int, [_P, _I64, _I64, _I64, _P, _I32, _P, _P]),
     "dvla_colsum_partial_rows": (_I64, []),
     "dvla_dropout": (C.c_int, [_P, _P, _I64, _I64, _F, _U32, _U32, _P]),

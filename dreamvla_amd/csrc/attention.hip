@@ -21,6 +21,7 @@
 // owns 32 keys, loops over query tiles; S = Q.K^T orientation so a lane owns one key and dK^T/dV^T
 // accumulate in registers).  No atomics; S is recomputed in each (7 MFMA passes instead of 5).
 #include "common.h"
+#include "launch.h"
 #include "../../include/dvla.h"
 
 namespace {
@@ -874,18 +875,14 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dkv_kernel(AttnKArgs p) {
   }
 }
 
-inline bool ok16(const void* ptr, int64_t s0, int64_t s1, int64_t s2) {
-  return (reinterpret_cast<uintptr_t>(ptr) % 16 == 0) && (s0 % 8 == 0) && (s1 % 8 == 0) && (s2 % 8 == 0);
-}
-
 int fill_args(const dvla_attn_params* q, AttnKArgs& a) {
   if (!q || !q->q || !q->k || !q->v || !q->o) return DVLA_ERR_ARG;
   if (q->B <= 0 || q->H <= 0 || q->Lq <= 0 || q->Lk <= 0) return DVLA_ERR_ARG;
   if (q->dropout_p < 0.f || q->dropout_p >= 1.f || !(q->scale > 0.f)) return DVLA_ERR_ARG;
   if ((int64_t)q->B * q->H * q->Lq >= (1LL << 31)) return DVLA_ERR_UNSUPPORTED;
-  if (!ok16(q->q, q->q_stride_b, q->q_stride_t, q->q_stride_h) || !ok16(q->k, q->k_stride_b, q->k_stride_t, q->k_stride_h) ||
-      !ok16(q->v, q->v_stride_b, q->v_stride_t, q->v_stride_h) ||
-      !(reinterpret_cast<uintptr_t>(q->o) % 8 == 0 && q->o_stride_b % 4 == 0 && q->o_stride_t % 4 == 0 && q->o_stride_h % 4 == 0))
+  if (!dvla_aligned(q->q, q->q_stride_b, q->q_stride_t, q->q_stride_h, 16) || !dvla_aligned(q->k, q->k_stride_b, q->k_stride_t, q->k_stride_h, 16) ||
+      !dvla_aligned(q->v, q->v_stride_b, q->v_stride_t, q->v_stride_h, 16) ||
+      !dvla_aligned(q->o, q->o_stride_b, q->o_stride_t, q->o_stride_h, 8))
     return DVLA_ERR_UNSUPPORTED;
   if (q->tile_map && !q->mask_bits_q) return DVLA_ERR_ARG;
   a.q = (const bf16_t*)q->q; a.k = (const bf16_t*)q->k; a.v = (const bf16_t*)q->v; a.o = (bf16_t*)q->o;
@@ -915,10 +912,10 @@ int fill_args(const dvla_attn_params* q, AttnKArgs& a) {
   a.dksb = q->dk_stride_b; a.dkst = q->dk_stride_t; a.dksh = q->dk_stride_h;
   a.dvsb = q->dv_stride_b; a.dvst = q->dv_stride_t; a.dvsh = q->dv_stride_h;
   a.fuse_delta = 0;
-  a.st16 = (ok16(q->o, q->o_stride_b, q->o_stride_t, q->o_stride_h) ? 1 : 0) |
-           ((q->dq && ok16(q->dq, q->dq_stride_b, q->dq_stride_t, q->dq_stride_h)) ? 2 : 0) |
-           ((q->dk && ok16(q->dk, q->dk_stride_b, q->dk_stride_t, q->dk_stride_h)) ? 4 : 0) |
-           ((q->dv && ok16(q->dv, q->dv_stride_b, q->dv_stride_t, q->dv_stride_h)) ? 8 : 0);
+  a.st16 = (dvla_aligned(q->o, q->o_stride_b, q->o_stride_t, q->o_stride_h, 16) ? 1 : 0) |
+           ((q->dq && dvla_aligned(q->dq, q->dq_stride_b, q->dq_stride_t, q->dq_stride_h, 16)) ? 2 : 0) |
+           ((q->dk && dvla_aligned(q->dk, q->dk_stride_b, q->dk_stride_t, q->dk_stride_h, 16)) ? 4 : 0) |
+           ((q->dv && dvla_aligned(q->dv, q->dv_stride_b, q->dv_stride_t, q->dv_stride_h, 16)) ? 8 : 0);
   return DVLA_OK;
 }
 
@@ -1745,14 +1742,7 @@ static bool attn_force_staged() {
 // DVLA_ATTN_SHORT=0 keeps short dense sequences on the two ring kernels (A/B measurements; read per launch)
 static bool attn_short_enabled() { const char* e = getenv("DVLA_ATTN_SHORT"); return !(e && e[0] == '0'); }
 static bool attn_short_fwd_enabled() { const char* e = getenv("DVLA_ATTN_SHORT_FWD"); return !(e && e[0] == '0'); }
-static int attn_num_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0; hipDeviceProp_t prop;
-    cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-  }
-  return cus;
-}
+static int attn_num_cus() { const int n = dvla_num_cus(); return n > 0 ? n : 256; }   // (256 = a whole MI355X when the query fails)
 
 // DVLA_ATTN_DBG=<bits>: ablation builds of the forward ring kernel (timing only, results garbage by design) -- compiled only
 // with -DDVLA_ATTN_ABLATION (DVLA_ABLATIONS=1 python -c 'import __graft_entry__ as g; g.build(force=True)'); the product library
@@ -1769,12 +1759,9 @@ static int attn_dbg() { const char* e = getenv("DVLA_ATTN_DBG"); return e ? atoi
 // tests/gpu_attn_items.py): 1 item 91.3 us, 2 items 84.7, 4 items 80.4, 8 items (384 workgroups: the chip half empty) 129.
 // DVLA_ATTN_ITEMS=<n> forces n items per workgroup (measurement).
 static dim3 ring_items_grid(int nblk, const AttnKArgs& a) {
-  static int forced = -1, cus = 0;
-  if (forced < 0) {
-    const char* e = getenv("DVLA_ATTN_ITEMS"); forced = e ? atoi(e) : 0;
-    int dev = 0; hipDeviceProp_t prop;
-    cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-  }
+  static int forced = -1;
+  if (forced < 0) { const char* e = getenv("DVLA_ATTN_ITEMS"); forced = e ? atoi(e) : 0; }
+  const int cus = attn_num_cus();
   const int nqb = nblk, items = a.B * a.H;
   int y = items;
   const bool tables = a.tile_map != nullptr || a.key_index != nullptr;
@@ -1799,13 +1786,7 @@ extern "C" int dvla_attn_fwd(const dvla_attn_params* q, void* stream_) {
       span_kv && !attn_force_staged()) {
     // short dense sequences (ViT L = 197, decoders 205 / 265): whole (batch, head) items per persistent workgroup, K / V read once
     const size_t sm = sf_smem_bytes(a.nqt);
-    static uint64_t attr_done = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!(attr_done & (1ull << dev))) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_short_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-      attr_done |= 1ull << dev;
-    }
+    (void)dvla_allow_lds(attn_fwd_short_kernel, 80 * 1024);
     const int64_t items = (int64_t)a.B * a.H;
     int64_t wgs = (int64_t)attn_num_cus() * 2;
     if (wgs > items) wgs = items;
@@ -1842,12 +1823,9 @@ extern "C" int dvla_attn_bwd(const dvla_attn_params* q, void* stream_) {
   if (rc != DVLA_OK) return rc;
   if (!q->dout || !q->lse || !q->delta || !q->dq || !q->dk || !q->dv) return DVLA_ERR_ARG;
   if (q->tile_map && !q->mask_bits_k) return DVLA_ERR_ARG;
-  if (!ok16(q->dout, q->do_stride_b, q->do_stride_t, q->do_stride_h)) return DVLA_ERR_UNSUPPORTED;
-  auto ok8 = [](const void* ptr, int64_t s0, int64_t s1, int64_t s2) {
-    return (reinterpret_cast<uintptr_t>(ptr) % 8 == 0) && (s0 % 4 == 0) && (s1 % 4 == 0) && (s2 % 4 == 0);
-  };
-  if (!ok8(q->dq, q->dq_stride_b, q->dq_stride_t, q->dq_stride_h) || !ok8(q->dk, q->dk_stride_b, q->dk_stride_t, q->dk_stride_h) ||
-      !ok8(q->dv, q->dv_stride_b, q->dv_stride_t, q->dv_stride_h) || !ok16(q->o, q->o_stride_b, q->o_stride_t, q->o_stride_h))
+  if (!dvla_aligned(q->dout, q->do_stride_b, q->do_stride_t, q->do_stride_h, 16)) return DVLA_ERR_UNSUPPORTED;
+  if (!dvla_aligned(q->dq, q->dq_stride_b, q->dq_stride_t, q->dq_stride_h, 8) || !dvla_aligned(q->dk, q->dk_stride_b, q->dk_stride_t, q->dk_stride_h, 8) ||
+      !dvla_aligned(q->dv, q->dv_stride_b, q->dv_stride_t, q->dv_stride_h, 8) || !dvla_aligned(q->o, q->o_stride_b, q->o_stride_t, q->o_stride_h, 16))
     return DVLA_ERR_UNSUPPORTED;
   const int64_t nrows = (int64_t)a.B * a.H * a.Lq;
   dim3 block(AT_THREADS);
@@ -1857,13 +1835,7 @@ extern "C" int dvla_attn_bwd(const dvla_attn_params* q, void* stream_) {
       !attn_force_staged()) {
     // short dense sequences (the dream-head decoders, L = 205 / 265): one pass per (batch, head), operands read once
     const size_t smem = sb_smem_bytes(a.nqt);
-    static uint64_t attr_done = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!(attr_done & (1ull << dev))) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_short_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr_done |= 1ull << dev;
-    }
+    (void)dvla_allow_lds(attn_bwd_short_kernel, 160 * 1024);
     int per_cu = (int)((size_t)(160 * 1024) / smem);
     if (per_cu < 1) per_cu = 1;
     if (per_cu > 2048 / SB_THREADS) per_cu = 2048 / SB_THREADS;
@@ -1895,15 +1867,7 @@ extern "C" int dvla_attn_bwd(const dvla_attn_params* q, void* stream_) {
   // (two workgroups of this kernel share a CU -- 186 VGPRs -- so a workgroup may take 80 KiB of its 160: the dropout tile keys
   // of a 930-token window are 15 KiB on top of 56)
   if (smem_dkv <= 80 * 1024 && span_q && !attn_force_staged()) {
-    if (smem_dkv > 64 * 1024) {
-      static uint64_t attr_done = 0;
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-      if (!(attr_done & (1ull << dev))) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_ring_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        attr_done |= 1ull << dev;
-      }
-    }
+    if (smem_dkv > 64 * 1024) (void)dvla_allow_lds(attn_bwd_dkv_ring_kernel, 80 * 1024);
     hipLaunchKernelGGL(attn_bwd_dkv_ring_kernel, grid_dkv, block, smem_dkv, stream, a);
   }
   else

@@ -16,6 +16,7 @@
 // Backward = delta kernel (rowsum dO.O) + dQ kernel (forward orientation) + dK/dV kernel (a wave owns 32 keys, S = Q.K^T so the
 // lane owns a key and dK^T / dV^T accumulate in registers).  No atomics, no host synchronisation, no allocation: capturable.
 #include "common.h"
+#include "launch.h"
 #include "../../include/dvla.h"
 
 namespace {
@@ -565,23 +566,6 @@ template <int DP> constexpr size_t hd_dq_smem() { return 2 * (size_t)(2 * HdTile
 template <int DP> constexpr size_t hd_dkv_smem() { return 2 * (size_t)HdDkv<DP>::BUF + HdDkv<DP>::KV_BYTES; }
 static_assert(hd_dkv_smem<128>() <= 160 * 1024 && hd_dkv_smem<96>() <= 160 * 1024, "dK/dV LDS"); 
 
-// dynamic LDS above the 64 KiB default needs the per-device attribute (set once per device and kernel)
-template <class K>
-void hd_allow_lds(K kernel, size_t bytes, uint64_t& done_mask) {
-  if (bytes <= 64 * 1024) return;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (done_mask & (1ull << dev)) return;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  done_mask |= 1ull << dev;
-}
-
-inline bool hd_ok16(const void* ptr, int64_t s0, int64_t s1, int64_t s2) {
-  return (reinterpret_cast<uintptr_t>(ptr) % 16 == 0) && (s0 % 8 == 0) && (s1 % 8 == 0) && (s2 % 8 == 0);
-}
-inline bool hd_ok8(const void* ptr, int64_t s0, int64_t s1, int64_t s2) {
-  return (reinterpret_cast<uintptr_t>(ptr) % 8 == 0) && (s0 % 4 == 0) && (s1 % 4 == 0) && (s2 % 4 == 0);
-}
 inline bool hd_supported(int D) { return D >= 8 && D <= 128 && D % 8 == 0 && D != 64; }
 
 int hd_fill(const dvla_attn_params* q, int head_dim, HdArgs& a) {
@@ -590,8 +574,8 @@ int hd_fill(const dvla_attn_params* q, int head_dim, HdArgs& a) {
   if (q->B <= 0 || q->H <= 0 || q->Lq <= 0 || q->Lk <= 0) return DVLA_ERR_ARG;
   if (q->dropout_p < 0.f || q->dropout_p >= 1.f || !(q->scale > 0.f)) return DVLA_ERR_ARG;
   if ((int64_t)q->B * q->H * q->Lq >= (1LL << 31) || q->B > 65535 || q->H > 65535) return DVLA_ERR_UNSUPPORTED;
-  if (!hd_ok16(q->q, q->q_stride_b, q->q_stride_t, q->q_stride_h) || !hd_ok16(q->k, q->k_stride_b, q->k_stride_t, q->k_stride_h) ||
-      !hd_ok16(q->v, q->v_stride_b, q->v_stride_t, q->v_stride_h) || !hd_ok8(q->o, q->o_stride_b, q->o_stride_t, q->o_stride_h))
+  if (!dvla_aligned(q->q, q->q_stride_b, q->q_stride_t, q->q_stride_h, 16) || !dvla_aligned(q->k, q->k_stride_b, q->k_stride_t, q->k_stride_h, 16) ||
+      !dvla_aligned(q->v, q->v_stride_b, q->v_stride_t, q->v_stride_h, 16) || !dvla_aligned(q->o, q->o_stride_b, q->o_stride_t, q->o_stride_h, 8))
     return DVLA_ERR_UNSUPPORTED;
   if (q->tile_map && !q->mask_bits_q) return DVLA_ERR_ARG;
   a.q = (const bf16_t*)q->q; a.k = (const bf16_t*)q->k; a.v = (const bf16_t*)q->v; a.o = (bf16_t*)q->o;
@@ -626,8 +610,7 @@ int hd_fill(const dvla_attn_params* q, int head_dim, HdArgs& a) {
 template <int DP>
 int hd_launch_fwd(const HdArgs& a, hipStream_t stream) {
   const dim3 grid((unsigned)((a.nqt + 3) / 4), (unsigned)a.H, (unsigned)a.B);
-  static uint64_t attr_done = 0;
-  hd_allow_lds(attn_hd_fwd_kernel<DP>, hd_fwd_smem<DP>(), attr_done);
+  (void)dvla_allow_lds(attn_hd_fwd_kernel<DP>, hd_fwd_smem<DP>());
   hipLaunchKernelGGL(attn_hd_fwd_kernel<DP>, grid, dim3(HD_THREADS), hd_fwd_smem<DP>(), stream, a);
   return dvla_check_launch();
 }
@@ -638,9 +621,8 @@ int hd_launch_bwd(const HdArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(attn_hd_delta_kernel, dim3((unsigned)((nrows * 8 + 255) / 256)), dim3(256), 0, stream, a);
   int rc = dvla_check_launch();
   if (rc != DVLA_OK) return rc;
-  static uint64_t dq_done = 0, dkv_done = 0;
-  hd_allow_lds(attn_hd_dq_kernel<DP>, hd_dq_smem<DP>(), dq_done);
-  hd_allow_lds(attn_hd_dkv_kernel<DP>, hd_dkv_smem<DP>(), dkv_done);
+  (void)dvla_allow_lds(attn_hd_dq_kernel<DP>, hd_dq_smem<DP>());
+  (void)dvla_allow_lds(attn_hd_dkv_kernel<DP>, hd_dkv_smem<DP>());
   const dim3 grid_dq((unsigned)((a.nqt + 3) / 4), (unsigned)a.H, (unsigned)a.B);
   hipLaunchKernelGGL(attn_hd_dq_kernel<DP>, grid_dq, dim3(HD_THREADS), hd_dq_smem<DP>(), stream, a);
   rc = dvla_check_launch();
@@ -671,9 +653,9 @@ extern "C" int dvla_attn_hd_bwd(const dvla_attn_params* q, int32_t head_dim, voi
   if (rc != DVLA_OK) return rc;
   if (!q->dout || !q->lse || !q->delta || !q->dq || !q->dk || !q->dv) return DVLA_ERR_ARG;
   if (q->tile_map && !q->mask_bits_k) return DVLA_ERR_ARG;
-  if (!hd_ok16(q->dout, q->do_stride_b, q->do_stride_t, q->do_stride_h) || !hd_ok16(q->o, q->o_stride_b, q->o_stride_t, q->o_stride_h) ||
-      !hd_ok8(q->dq, q->dq_stride_b, q->dq_stride_t, q->dq_stride_h) || !hd_ok8(q->dk, q->dk_stride_b, q->dk_stride_t, q->dk_stride_h) ||
-      !hd_ok8(q->dv, q->dv_stride_b, q->dv_stride_t, q->dv_stride_h))
+  if (!dvla_aligned(q->dout, q->do_stride_b, q->do_stride_t, q->do_stride_h, 16) || !dvla_aligned(q->o, q->o_stride_b, q->o_stride_t, q->o_stride_h, 16) ||
+      !dvla_aligned(q->dq, q->dq_stride_b, q->dq_stride_t, q->dq_stride_h, 8) || !dvla_aligned(q->dk, q->dk_stride_b, q->dk_stride_t, q->dk_stride_h, 8) ||
+      !dvla_aligned(q->dv, q->dv_stride_b, q->dv_stride_t, q->dv_stride_h, 8))
     return DVLA_ERR_UNSUPPORTED;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   switch ((head_dim + 31) / 32) {

@@ -8,6 +8,7 @@
 // Same arithmetic as attention.hip (and as oracle/torch_ref.py::attention_bf16): scores in fp32, integer running maximum in the
 // log2 domain, row sum of the unrounded probabilities, P and dS rounded to bf16 where they enter the second product.
 #include "common.h"
+#include "launch.h"
 #include "../../include/dvla.h"
 
 namespace {
@@ -119,16 +120,6 @@ constexpr size_t SMALL_LDS_LIMIT = 160 * 1024;
 inline size_t small_fwd_smem(int L, int D) { return ((size_t)3 * L * (D + 1) + (size_t)L * (L + 1)) * 4; }
 inline size_t small_bwd_smem(int L, int D) { return ((size_t)4 * L * (D + 1) + (size_t)2 * L * (L + 1)) * 4; }
 
-// hipFuncSetAttribute is per device: remember which devices have it (a process may drive several)
-template <class K>
-void small_allow_lds(K kernel, uint64_t& done_mask) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (done_mask & (1ull << dev)) return;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMALL_LDS_LIMIT);
-  done_mask |= 1ull << dev;
-}
-
 int fill(const dvla_attn_params* q, int head_dim, SmallArgs& a) {
   if (!q || !q->q || !q->k || !q->v || !q->o) return DVLA_ERR_ARG;
   if (q->B <= 0 || q->H <= 0 || q->Lq <= 0 || q->Lk != q->Lq || !(q->scale > 0.f)) return DVLA_ERR_ARG;
@@ -160,8 +151,7 @@ extern "C" int dvla_attn_small_fwd(const dvla_attn_params* q, int32_t head_dim, 
   int rc = fill(q, head_dim, a);
   if (rc != DVLA_OK) return rc;
   const size_t smem = small_fwd_smem(a.L, a.D);
-  static uint64_t attr_done = 0;
-  small_allow_lds(attn_small_fwd_kernel, attr_done);
+  (void)dvla_allow_lds(attn_small_fwd_kernel, SMALL_LDS_LIMIT);
   hipLaunchKernelGGL(attn_small_fwd_kernel, dim3((unsigned)a.H, (unsigned)a.B), dim3(64), smem, reinterpret_cast<hipStream_t>(stream_), a);
   return dvla_check_launch();
 }
@@ -172,8 +162,7 @@ extern "C" int dvla_attn_small_bwd(const dvla_attn_params* q, int32_t head_dim, 
   if (rc != DVLA_OK) return rc;
   if (!q->dout || !q->lse || !q->dq || !q->dk || !q->dv) return DVLA_ERR_ARG;
   const size_t smem = small_bwd_smem(a.L, a.D);
-  static uint64_t attr_done = 0;
-  small_allow_lds(attn_small_bwd_kernel, attr_done);
+  (void)dvla_allow_lds(attn_small_bwd_kernel, SMALL_LDS_LIMIT);
   hipLaunchKernelGGL(attn_small_bwd_kernel, dim3((unsigned)a.H, (unsigned)a.B), dim3(64), smem, reinterpret_cast<hipStream_t>(stream_), a);
   return dvla_check_launch();
 }

@@ -34,6 +34,7 @@
 //   guidance + DDIM update (csrc/elementwise.hip ddim_cfg_step_kernel, operation by operation) and the next step's token
 //   embedding run on team member 0 between two steps.  One launch = the whole sampler: steps x (1 + 5 x depth) exchanges.
 #include "common.h"
+#include "launch.h"
 #include "../../include/dvla.h"
 
 namespace {
@@ -761,9 +762,8 @@ static int dit_sample_launch(const dvla_dit_sample_params* q, int fm, void* stre
   constexpr int KS = 3, RB = 1;
   if (q->workspace_bytes < dvla_dit_sample_workspace_bytes(q->hidden) || (reinterpret_cast<uintptr_t>(q->workspace) & 15))
     return DVLA_ERR_ARG;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return DVLA_ERR_LAUNCH;
+  const int cus = dvla_num_cus();
+  if (cus <= 0) return DVLA_ERR_LAUNCH;
   if (cus < 8 * TEAM) return DVLA_ERR_UNSUPPORTED;      // the team is the 32 CUs of one XCD of a whole MI355X
   Args a;
   a.blocks = q->blocks;
@@ -787,15 +787,9 @@ static int dit_sample_launch(const dvla_dit_sample_params* q, int fm, void* stre
   const size_t lds = smem > 81920 ? smem : 81920;
   static int ahead = -1;
   if (ahead < 0) { const char* e = getenv("DVLA_DIT_AHEAD"); ahead = e ? atoi(e) : 1; }      // 0: the call-per-phase kernel (A/B)
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)dit_team_kernel_ahead<KS, RB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)dit_team_kernel<KS, RB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)dit_team_kernel_ahead<KS, RB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)dit_team_kernel<KS, RB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return DVLA_ERR_LAUNCH;
-    attr_set = true;
-  }
+  if (!dvla_allow_lds(dit_team_kernel_ahead<KS, RB, false>, 160 * 1024) || !dvla_allow_lds(dit_team_kernel<KS, RB, false>, 160 * 1024) ||
+      !dvla_allow_lds(dit_team_kernel_ahead<KS, RB, true>, 160 * 1024) || !dvla_allow_lds(dit_team_kernel<KS, RB, true>, 160 * 1024))
+    return DVLA_ERR_LAUNCH;
   const dim3 grid((unsigned)(8 * TEAM)), block(64 * NWAVES);
   if (fm) {
     if (ahead) hipLaunchKernelGGL((dit_team_kernel_ahead<KS, RB, true>), grid, block, lds, stream, a);

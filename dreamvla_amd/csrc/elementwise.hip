@@ -232,12 +232,6 @@ int dvla_reduce_partial_rows(const float* partial, int nrows, int64_t cols, int6
 }
 
 extern "C" int dvla_colsum_dt(const void* x, int64_t ld, int64_t rows, int64_t cols, void* out, int32_t out_dtype,
-                              float* partial, void* stream_);
-extern "C" int dvla_colsum(const void* x, int64_t ld, int64_t rows, int64_t cols, float* out, float* partial, void* stream_) {
-  return dvla_colsum_dt(x, ld, rows, cols, out, DVLA_DT_F32, partial, stream_);
-}
-
-extern "C" int dvla_colsum_dt(const void* x, int64_t ld, int64_t rows, int64_t cols, void* out, int32_t out_dtype,
                               float* partial, void* stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (!x || !out || !partial || rows < 0 || cols <= 0) return DVLA_ERR_ARG;

@@ -1,5 +1,6 @@
-// gemm.hip -- host-side dispatcher of the bf16 GEMM kernels (kernel templates: gemm_impl.h; their instantiations are
-// compiled one (configuration, operand layout) per translation unit in gemm_inst_*.hip so that the build runs in parallel).
+// gemm.hip -- host-side dispatcher of the bf16 GEMM kernels (kernel templates: gemm_impl.h, gemm_phase.h).  Their instantiations
+// are named once, in gemm_inst_list.h: declared `extern template` here, and compiled one per translation unit from gemm_inst.hip
+// (-DDVLA_INST=<entry>) so that the build runs in parallel.
 #include <stdlib.h>
 
 #include <mutex>

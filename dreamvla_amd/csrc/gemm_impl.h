@@ -35,6 +35,7 @@
 
 #pragma once
 #include "common.h"
+#include "launch.h"
 #include "../../include/dvla.h"
 #include <type_traits>
 
@@ -1462,37 +1463,20 @@ inline int64_t persistent_grid(int64_t items, int64_t slots) {
   return (items + per - 1) / per;
 }
 
-inline int num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
+inline int num_cus() { const int n = dvla_num_cus(); return n > 0 ? n : 256; }
 
 template <class CF, bool A_T, bool B_T>
 void launch_one(const GemmKArgs& a, int split_k, hipStream_t stream) {
-  static bool attr_set = false;
   auto kern = &gemm_kernel<CF, A_T, B_T>;
-  if (!attr_set) {  // > 64 KiB of LDS per workgroup needs the opt-in (160 KiB per CU on gfx950)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM_BYTES);
-    attr_set = true;
-  }
+  (void)dvla_allow_lds(kern, CF::SMEM_BYTES);   // > 64 KiB of LDS per workgroup needs the opt-in (160 KiB per CU on gfx950)
   dim3 grid((unsigned)(a.tiles_m * a.tiles_n), (unsigned)split_k, 1), block(CF::NT, 1, 1);
   hipLaunchKernelGGL(kern, grid, block, CF::SMEM_BYTES, stream, a);
 }
 
 template <class RC, bool A_T, bool B_T, int EPI>
 void launch_ring_one(const GemmKArgs& a, int split_k, hipStream_t stream) {
-  static bool attr_set = false;
   auto kern = &gemm_ring_kernel<RC, A_T, B_T, EPI>;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, RC::SMEM_BYTES);
-    attr_set = true;
-  }
+  (void)dvla_allow_lds(kern, RC::SMEM_BYTES);
   const int64_t items = (int64_t)a.tiles_m * a.tiles_n * split_k;
   dim3 grid((unsigned)persistent_grid(items, (int64_t)num_cus() * RC::WG_PER_CU), 1, 1), block(RC::NT, 1, 1);
   hipLaunchKernelGGL(kern, grid, block, RC::SMEM_BYTES, stream, a);

@@ -647,12 +647,8 @@ void gemm_phase_kernel(GemmKArgs p) {
 
 template <bool A_T, bool B_T, int EPI, int FEAT = 0>
 void launch_phase_one(const GemmKArgs& a, int split_k, hipStream_t stream) {
-  static bool attr_set = false;
   auto kern = &gemm_phase_kernel<A_T, B_T, EPI, FEAT>;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, PCfg::SMEM_BYTES);
-    attr_set = true;
-  }
+  (void)dvla_allow_lds(kern, PCfg::SMEM_BYTES);
   const int64_t items = (int64_t)a.tiles_m * a.tiles_n * split_k;
   const int64_t slots = (int64_t)num_cus();
   const int64_t nwg = a.sk_tiles > 0 ? slots : persistent_grid(items, slots);   // stream-K: exactly one workgroup per CU

@@ -307,15 +307,6 @@ static bool ln_groups_ok(int64_t rows, int32_t grp, int32_t gstride, int32_t gof
 
 extern "C" int dvla_layernorm_fwd_rows(const void* x, const void* gamma, const void* beta, int32_t param_dtype, void* y,
                                        float* mean, float* rstd, int64_t rows, int64_t cols, float eps,
-                                       int32_t grp, int32_t gstride, int32_t goff, int32_t map_output, void* stream_);
-
-extern "C" int dvla_layernorm_fwd(const void* x, const void* gamma, const void* beta, int32_t param_dtype, void* y,
-                                  float* mean, float* rstd, int64_t rows, int64_t cols, float eps, void* stream_) {
-  return dvla_layernorm_fwd_rows(x, gamma, beta, param_dtype, y, mean, rstd, rows, cols, eps, 0, 0, 0, 0, stream_);
-}
-
-extern "C" int dvla_layernorm_fwd_rows(const void* x, const void* gamma, const void* beta, int32_t param_dtype, void* y,
-                                       float* mean, float* rstd, int64_t rows, int64_t cols, float eps,
                                        int32_t grp, int32_t gstride, int32_t goff, int32_t map_output, void* stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (map_output && grp == 0) return DVLA_ERR_ARG;
@@ -336,18 +327,6 @@ extern "C" int dvla_layernorm_fwd_rows(const void* x, const void* gamma, const v
     default: hipLaunchKernelGGL(ln_fwd_kernel<4>, grid, block, 0, stream, xp, gamma, beta, pf32, yp, mean, rstd, rows, (int)cols, eps, grp, gstride, goff, map_output ? 1 : 0); break;
   }
   return dvla_check_launch();
-}
-
-extern "C" int dvla_layernorm_bwd_add(const void* dy, const void* x, const void* gamma, int32_t param_dtype,
-                                      const float* mean, const float* rstd, const void* dres, void* dx, void* dgamma,
-                                      void* dbeta, int32_t grad_dtype, float* partial, int64_t rows, int64_t cols,
-                                      void* stream_);
-
-extern "C" int dvla_layernorm_bwd(const void* dy, const void* x, const void* gamma, int32_t param_dtype,
-                                  const float* mean, const float* rstd, void* dx, float* dgamma, float* dbeta,
-                                  float* partial, int64_t rows, int64_t cols, void* stream_) {
-  return dvla_layernorm_bwd_add(dy, x, gamma, param_dtype, mean, rstd, nullptr, dx, dgamma, dbeta, DVLA_DT_F32, partial, rows,
-                                cols, stream_);
 }
 
 static int ln_bwd_launch(const void* dy, const void* x, const void* gamma, int32_t param_dtype, const float* mean, const float* rstd,

@@ -1679,7 +1679,7 @@ class _AssembleTokens(torch.autograd.Function):
 class _ConcatSharedSuffix(torch.autograd.Function):
     """[prefix_b ; suffix] for every sequence b: (n, nq, D) and ONE (ns, D) block shared by all sequences -> (n, nq + ns, D).
     Forward = one gather-write pass (dvla_assemble_tokens with a zero batch stride for the suffix: write-bound); backward =
-    a slice for the prefix and ONE column-sum pass over the batch for the suffix (dvla_colsum on the (n, ns * D) window of the
+    a slice for the prefix and ONE column-sum pass over the batch for the suffix (dvla_colsum_dt on the (n, ns * D) window of the
     gradient).  torch.cat((prefix, suffix.expand(n, ...))) + autograd's expand-backward moved the same bytes at a third of the
     bandwidth (the dream-head decoders build a 564-MB qkv buffer this way: 2.7 ms of cat kernels per training step)."""
 

@@ -39,8 +39,10 @@ extern "C" {
  * with a clear message instead of a missing-symbol error).  3 = round 3 (dvla_last_gemm_variant, variant 10, ...); 4 = k-sums on the
  * weight-gradient GEMM (ksum_* fields of dvla_gemm_params); 5 = dvla_ddim_cfg_step, dvla_act_bwd_colsum, a_layernorm,
  * GEMM configuration 11; 6 = dvla_dit_sample (the evaluation sampler as one persistent kernel); 7 = round 5: the sampler's
- * status word no longer carries over to the next launch (workspace words 33 / 34), dvla_dit_sample_inject_timeouts. */
-#define DVLA_ABI_VERSION 8
+ * status word no longer carries over to the next launch (workspace words 33 / 34), dvla_dit_sample_inject_timeouts;
+ * 9 = the three entry points that were aliases of a general form with fixed arguments (plain LayerNorm forward / backward, fp32
+ * column sum) are removed: call dvla_layernorm_fwd_rows, dvla_layernorm_bwd_add and dvla_colsum_dt. */
+#define DVLA_ABI_VERSION 9
 int dvla_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------------
@@ -102,7 +104,7 @@ typedef struct dvla_gemm_params {
    * the operand stored k-major (a_trans / b_trans = 1); otherwise DVLA_ERR_UNSUPPORTED. */
   void* ksum; int32_t ksum_dtype; int32_t ksum_operand; float* ksum_workspace;
   /* (ABI 5) a_layernorm != 0: the rows of A are layer-normalised on their way into the product -- A'(m, :) = (A(m, :) - mean_m) *
-   * rsqrt(var_m + a_ln_eps), no affine parameters, rounded to bf16 like the output of dvla_layernorm_fwd -- i.e. the GEMM computes
+   * rsqrt(var_m + a_ln_eps), no affine parameters, rounded to bf16 like the output of dvla_layernorm_fwd_rows -- i.e. the GEMM computes
    * Linear(LayerNorm(x)) from x.  The DiT blocks' parameter-free LayerNorms in front of qkv / fc1 / the output layer
    * (models/action_model/models.py:129-141,158-160) at evaluation: 250 launches of a control step less.  Few-rows kernel only
    * (configuration 11: M <= 512, k-contiguous operands, 512 <= K <= 1536); DVLA_ERR_UNSUPPORTED otherwise. */
@@ -153,13 +155,9 @@ void dvla_get_gemm_schedule(int* oversubscribe, int* stream_k);
  * bwd: dx (NULL, round 6: the input needs no gradient -- parameter gradients only); dgamma/dbeta (fp32, cols) when non-NULL, using
  *      `partial` = fp32 workspace of
  *      2 * dvla_layernorm_bwd_partial_rows() * cols floats.
+ * Forward over all rows of a buffer: dvla_layernorm_fwd_rows with grp = gstride = goff = map_output = 0 (below).
  */
-int dvla_layernorm_fwd(const void* x, const void* gamma, const void* beta, int32_t param_dtype, void* y,
-                       float* mean, float* rstd, int64_t rows, int64_t cols, float eps, void* stream);
-int dvla_layernorm_bwd(const void* dy, const void* x, const void* gamma, int32_t param_dtype,
-                       const float* mean, const float* rstd, void* dx, float* dgamma, float* dbeta,
-                       float* partial, int64_t rows, int64_t cols, void* stream);
-/* same, plus the gradient of the residual stream that bypassed the LayerNorm (pre-LN blocks: h = x + f(LN(x)), so
+/* backward, plus the gradient of the residual stream that bypassed the LayerNorm (pre-LN blocks: h = x + f(LN(x)), so
  * dL/dx = dL/dh + LN'(...)): dx = dres + LN-backward(dy), one bf16 rounding -- replaces the separate autograd
  * accumulation add after every norm1 / norm2 / ln_1 / ln_2 backward (models/gpt2.py:312-339, timm Block).  dres must
  * not overlap dx; dres == NULL gives plain LayerNorm backward.  dgamma / dbeta are written in `grad_dtype` (0 = bf16:
@@ -253,10 +251,8 @@ int dvla_attn_hd_bwd(const dvla_attn_params* p, int32_t head_dim, void* stream);
 /* ---------------------------------------------------------------------------------------------------
  * Small HBM-bound helpers (bf16 unless noted).
  */
-/* out[n] = sum_m x[m,n]  (bias gradients).  out fp32; `partial` = fp32 workspace of
- * dvla_colsum_partial_rows() * cols floats. */
-int dvla_colsum(const void* x, int64_t ld, int64_t rows, int64_t cols, float* out, float* partial, void* stream);
-/* same with `out` written in out_dtype (0 = bf16: the bias gradient in the parameter's dtype, no cast kernel; 1 = fp32) */
+/* out[n] = sum_m x[m,n]  (bias gradients), written in out_dtype (0 = bf16: the bias gradient in the parameter's dtype, no cast
+ * kernel; 1 = fp32); `partial` = fp32 workspace of dvla_colsum_partial_rows() * cols floats. */
 int dvla_colsum_dt(const void* x, int64_t ld, int64_t rows, int64_t cols, void* out, int32_t out_dtype, float* partial,
                    void* stream);
 int64_t dvla_colsum_partial_rows(void);

@@ -545,7 +545,7 @@ def check_gemm_tail(**kw):
 
 def check_gemm_ln(M, N, K, bias=True, act="none", residual=False, eps=1e-6, seed=0):
     """dvla_gemm_bf16 with a_layernorm: Linear(LayerNorm(x)) from x in one launch (the DiT blocks' parameter-free LayerNorms at
-    evaluation).  Oracle: F.layer_norm without affine -> rounded to bf16 (what dvla_layernorm_fwd writes) -> the GEMM epilogue."""
+    evaluation).  Oracle: F.layer_norm without affine -> rounded to bf16 (what dvla_layernorm_fwd_rows writes) -> the GEMM epilogue."""
     from dreamvla_amd import _lib, ops
     from dreamvla_amd._lib import ACT
     g = torch.Generator().manual_seed(4321 + seed)

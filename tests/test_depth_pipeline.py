@@ -58,7 +58,7 @@ def test_test_data_holds_the_values_it_promises():
 def test_symbol_and_abi_version():
     from dreamvla_amd import _lib
     assert "dvla_depth_preprocess" in _lib.SYMBOLS
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
     assert callable(P.preprocess_depth)
 
 

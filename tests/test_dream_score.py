@@ -103,7 +103,7 @@ def test_entry_points_are_exported_and_bound_as_declared(symbol):
     from dreamvla_amd import _lib
     lib = ctypes.CDLL(_lib.LIB_PATH)
     assert hasattr(lib, symbol)
-    assert lib.dvla_abi_version() == 8 == _lib.ABI_VERSION                  # additive: the ABI version does not move
+    assert lib.dvla_abi_version() == 9 == _lib.ABI_VERSION                  # the version include/dvla.h declares
     ret, decl = re.search(r"(int64_t|int)\s+%s\s*\((.*?)\)\s*;" % symbol, _header(), flags=re.S).groups()
     want = []
     for arg in decl.split(","):

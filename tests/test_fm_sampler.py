@@ -36,7 +36,7 @@ def test_binding_of_the_new_entry_points():
     assert re.search(r"int dvla_fm_cfg_step\(const void\* model_out, int64_t sample_stride, const float\* x, float\* x_next, "
                      r"int64_t bs, int64_t per_sample,\s+float cfg_scale, float delta, void\* stream\);", txt)
     assert "int dvla_dit_sample_fm(const dvla_dit_sample_params* p, void* stream);" in txt
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
 
 
 def _bf16(a):

@@ -51,7 +51,7 @@ def test_bicubic_tables(pair):
 
 def test_device_entry_is_bound_and_has_no_cpu_fallback():
     from dreamvla_amd import _lib
-    assert "dvla_image_resize_u8" in _lib.SYMBOLS and _lib.ABI_VERSION == 8
+    assert "dvla_image_resize_u8" in _lib.SYMBOLS and _lib.ABI_VERSION == 9
     with pytest.raises(_lib.DvlaError):
         P.resize_frames_u8(torch.zeros(1, 200, 200, 3, dtype=torch.uint8))
     with pytest.raises(TypeError):

@@ -52,14 +52,14 @@ def test_header_and_library_export_the_master_kernels():
     assert _lib.SYMBOLS["dvla_sumsq_f32"] == (ctypes.c_int, [P, ctypes.c_int64, P, P, ctypes.c_int32, P])
     assert _lib.SYMBOLS["dvla_adamw_f32_master"] == (ctypes.c_int, [P, P, P, P, P, ctypes.c_int64, D, D, D, D, D, ctypes.c_int64,
                                                                     P, ctypes.c_float, P])
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
     if not os.path.exists(LIB):
         pytest.skip("library not built")
     lib = _lib.load()
     for name in ("dvla_sumsq_f32", "dvla_adamw_f32_master"):
         fn = getattr(lib, name)
         assert fn.restype is _lib.SYMBOLS[name][0] and list(fn.argtypes) == _lib.SYMBOLS[name][1]
-    assert lib.dvla_abi_version() == 8
+    assert lib.dvla_abi_version() == 9
 
 
 @pytest.mark.parametrize("max_norm", [None, 0.1], ids=["clip_off", "clip_on"])

@@ -95,7 +95,7 @@ def test_table_store_layout():
 def test_device_entry_is_bound_and_arguments_are_checked_before_any_launch():
     from dreamvla_amd import _lib
     from dreamvla_amd.vit_mae import MAEFrameAugment
-    assert "dvla_image_resized_crop" in _lib.SYMBOLS and _lib.ABI_VERSION == 8
+    assert "dvla_image_resized_crop" in _lib.SYMBOLS and _lib.ABI_VERSION == 9
     f = torch.zeros(2, 20, 30, 3, dtype=torch.uint8)
     good = torch.tensor([[0, 0, 20, 30, 0], [3, 4, 5, 6, 1]], dtype=torch.int32)
     for fn in (P.resized_crop_u8, P.resized_crop):
