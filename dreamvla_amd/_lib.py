@@ -97,6 +97,24 @@ class MaeLossParams(C.Structure):
                 ("mask", C.c_void_p), ("N", C.c_int64)]
 
 
+STEP_MAX_BUCKETS, STEP_MAX_CANDIDATES = 256, 9      # DVLA_STEP_MAX_* of include/dvla.h
+
+
+class StepScalars(C.Structure):
+    _fields_ = [("inv_bc1", C.c_float), ("inv_bc2_sqrt", C.c_float), ("bc2_sqrt", C.c_float), ("step_size", C.c_float)]
+
+
+class StepState(C.Structure):
+    """dvla_step_state (device memory; this mirror gives the offsets).  The first STEP_READBACK_BYTES are the per-step readback."""
+    _fields_ = [("applied", C.c_int64), ("skipped", C.c_int64), ("faults", C.c_int64), ("ok", C.c_int32), ("sumsq", C.c_float),
+                ("cand", C.c_int32), ("n_latched", C.c_int32),
+                ("inv_bc1", C.c_float), ("inv_bc2_sqrt", C.c_float), ("bc2_sqrt", C.c_float), ("step_size", C.c_float),
+                ("latched_step", C.c_int64), ("skipped_bucket_sumsq", C.c_float * STEP_MAX_BUCKETS)]
+
+
+STEP_READBACK_BYTES = 32
+
+
 # every symbol include/dvla.h declares: (name, restype, argtypes)
 _P, _I64, _I32, _F, _U32 = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_uint32
 SYMBOLS = {
@@ -167,6 +185,12 @@ SYMBOLS = {
                                   C.c_float, _P]),
     "dvla_adamw_f32_master": (C.c_int, [_P, _P, _P, _P, _P, _I64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                         _I64, _P, C.c_float, _P]),
+    "dvla_step_candidates": (C.c_int, [C.c_double, C.c_double, C.c_double, _I64, _I32, C.POINTER(StepScalars)]),
+    "dvla_step_verdict": (C.c_int, [_P, _I32, _P, _P, _I64, _I32, C.POINTER(StepScalars), _P]),
+    "dvla_adamw_bf16_guarded": (C.c_int, [_P, _P, _P, _P, _I64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                          _P, _P]),
+    "dvla_adamw_f32_master_guarded": (C.c_int, [_P, _P, _P, _P, _P, _I64, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                C.c_double, C.c_float, _P, _P]),
 }
 
 _lib = None

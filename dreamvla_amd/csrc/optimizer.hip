@@ -16,6 +16,12 @@
 //   dvla_adamw_f32_master : clip (in fp32) + AdamW restating torch's foreach AdamW on fp32 parameters operation for
 //                           operation, and the bf16 compute shadow of the new master written in the same pass:
 //                           4 B (g) + 3 x (4 + 4) B (p, m, v) + 2 B (shadow) = 30 B / parameter.
+//
+// guarded step (an addition; dvla.h): the per-bucket sums go into one slot each,
+//   dvla_step_verdict             : one wave adds them, decides whether the step is applied (the total is finite), counts, and
+//                                   picks the bias-correction scalars of the step count that is then current from a table the
+//                                   host derived (dvla_step_candidates) for every count still possible
+//   dvla_adamw_*_guarded          : the two AdamW kernels reading verdict and scalars from that state; a skipped step moves no byte
 #include "common.h"
 #include "../../include/dvla.h"
 
@@ -150,7 +156,8 @@ __device__ __forceinline__ void master_one(float& p, float g, float& m, float& v
   p = fmaf(a.step_size, __fdiv_rn(m, denom), p);                // p.addcdiv_(m, denom, -lr / bc1)
 }
 
-__global__ __launch_bounds__(256) void adamw_master_kernel(MasterArgs a) {
+// the whole of adamw_master_kernel: the guarded kernel runs the same body on an applied step
+__device__ __forceinline__ void adamw_master_body(MasterArgs a) {
   float coef = 1.0f;
   if (a.sumsq) {
     const float c = a.max_norm / (sqrtf(a.sumsq[0]) + 1e-6f);
@@ -187,7 +194,117 @@ __global__ __launch_bounds__(256) void adamw_master_kernel(MasterArgs a) {
     }
 }
 
+__global__ __launch_bounds__(256) void adamw_master_kernel(MasterArgs a) { adamw_master_body(a); }
+
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// The step-dependent scalars of the two AdamW kernels, from the 1-based step count.  dvla_adamw_bf16 / dvla_adamw_f32_master
+// and dvla_step_candidates all derive them here, so a guarded step that selects candidate `step` runs on the same floats.
+inline void bf16_step_scalars(float beta1, float beta2, int64_t step, float* inv_bc1, float* inv_bc2_sqrt) {
+  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+  *inv_bc1 = (float)(1.0 / bc1); *inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+}
+inline void master_fixed_scalars(MasterArgs& a, double lr, double beta1, double beta2, double eps, double weight_decay) {
+  a.decay = (float)(1.0 - lr * weight_decay);
+  a.w1 = (float)(1.0 - beta1);
+  a.w1_small = fabsf(a.w1) < 0.5f;
+  a.beta2 = (float)beta2;
+  a.omb2 = (float)(1.0 - beta2);
+  a.eps = (float)eps;
+}
+inline void master_step_scalars(double lr, double beta1, double beta2, int64_t step, float* bc2_sqrt, float* step_size) {
+  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+  *bc2_sqrt = (float)pow(bc2, 0.5);
+  *step_size = (float)((lr / bc1) * -1.0);
+}
+
+// ---- guarded step: the verdict of one step and the AdamW kernels that obey it (dvla.h: dvla_step_state) ---------------------
+struct VerdictArgs {
+  const float* slots; int n; float* out; dvla_step_state* st; int64_t confirmed; int n_cand;
+  dvla_step_scalars c[DVLA_STEP_MAX_CANDIDATES];      // by value: no upload, no pointer to chase
+};
+
+// One wave.  Lane 0 adds the per-bucket sums in index order (the order of the `accumulate` chain of dvla_sumsq_*, so the
+// total has the same bits), decides, picks the candidate scalars and moves the counters; all lanes latch the slots of a skip.
+__global__ __launch_bounds__(64) void step_verdict_kernel(VerdictArgs a) {
+  __shared__ float slot[DVLA_STEP_MAX_BUCKETS];
+  __shared__ int verdict;
+  for (int i = threadIdx.x; i < a.n; i += 64) slot[i] = a.slots[i];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = slot[0];
+    for (int i = 1; i < a.n; ++i) t = t + slot[i];
+    int ok = (__float_as_uint(t) & 0x7f800000u) != 0x7f800000u;      // finite: exponent not all ones
+    const int64_t j = a.st->applied - a.confirmed;
+    dvla_step_scalars s = a.c[0];
+#pragma unroll
+    for (int k = 1; k < DVLA_STEP_MAX_CANDIDATES; ++k)               // compare-and-select: a.c[j] would go through scratch
+      if (j == k) s = a.c[k];
+    if (j < 0 || j >= a.n_cand) {                                    // the host's window does not cover this step
+      ok = 0;
+      a.st->faults += 1;
+    } else {
+      a.st->cand = (int32_t)j;
+      a.st->inv_bc1 = s.inv_bc1; a.st->inv_bc2_sqrt = s.inv_bc2_sqrt; a.st->bc2_sqrt = s.bc2_sqrt; a.st->step_size = s.step_size;
+    }
+    a.out[0] = t;
+    a.st->sumsq = t;
+    a.st->ok = ok;
+    a.st->applied += ok;
+    a.st->skipped += !ok;
+    if (!ok) { a.st->n_latched = a.n; a.st->latched_step = a.st->applied + a.st->skipped; }
+    verdict = ok;
+  }
+  __syncthreads();
+  if (!verdict)
+    for (int i = threadIdx.x; i < a.n; i += 64) a.st->skipped_bucket_sumsq[i] = slot[i];
+}
+
+// adamw_kernel / adamw_master_kernel under a verdict: nothing is read or written on a skipped step; on an applied one the
+// step-dependent scalars come from the state and the twin's loop runs.  a.sumsq is &st->sumsq or null.
+// The bf16 loop is restated here (every element still goes through adam_one): moved into a function shared with adamw_kernel
+// it compiles adamw_kernel to a different instruction stream, and the unguarded kernels are to stay as they are; the master
+// kernels share adamw_master_body, which leaves adamw_master_kernel's instructions unchanged.
+__global__ __launch_bounds__(256) void adamw_guarded_kernel(AdamArgs a, const dvla_step_state* __restrict__ st) {
+  if (st->ok == 0) return;
+  a.inv_bc1 = st->inv_bc1; a.inv_bc2_sqrt = st->inv_bc2_sqrt;
+  float coef = 1.0f;
+  if (a.sumsq) {
+    const float c = a.max_norm / (sqrtf(a.sumsq[0]) + 1e-6f);
+    coef = c < 1.0f ? c : 1.0f;
+  }
+  const int64_t nvec = a.n >> 3;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
+    const uint4 up = reinterpret_cast<const uint4*>(a.p)[i], ug = reinterpret_cast<const uint4*>(a.g)[i];
+    const uint4 um = reinterpret_cast<const uint4*>(a.m)[i], uv = reinterpret_cast<const uint4*>(a.v)[i];
+    const uint32_t wp[4] = {up.x, up.y, up.z, up.w}, wg[4] = {ug.x, ug.y, ug.z, ug.w};
+    const uint32_t wm[4] = {um.x, um.y, um.z, um.w}, wv[4] = {uv.x, uv.y, uv.z, uv.w};
+    uint32_t op[4], om[4], ov[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float p0 = bf2f((bf16_t)(wp[k] & 0xffff)), p1 = bf2f((bf16_t)(wp[k] >> 16));
+      float m0 = bf2f((bf16_t)(wm[k] & 0xffff)), m1 = bf2f((bf16_t)(wm[k] >> 16));
+      float v0 = bf2f((bf16_t)(wv[k] & 0xffff)), v1 = bf2f((bf16_t)(wv[k] >> 16));
+      adam_one(p0, bf2f((bf16_t)(wg[k] & 0xffff)), m0, v0, a, coef);
+      adam_one(p1, bf2f((bf16_t)(wg[k] >> 16)), m1, v1, a, coef);
+      op[k] = pack2bf(p0, p1); om[k] = pack2bf(m0, m1); ov[k] = pack2bf(v0, v1);
+    }
+    reinterpret_cast<uint4*>(a.p)[i] = make_uint4(op[0], op[1], op[2], op[3]);
+    reinterpret_cast<uint4*>(a.m)[i] = make_uint4(om[0], om[1], om[2], om[3]);
+    reinterpret_cast<uint4*>(a.v)[i] = make_uint4(ov[0], ov[1], ov[2], ov[3]);
+  }
+  if (blockIdx.x == 0)
+    for (int64_t i = (nvec << 3) + threadIdx.x; i < a.n; i += 256) {
+      float p = bf2f(a.p[i]), m = bf2f(a.m[i]), v = bf2f(a.v[i]);
+      adam_one(p, bf2f(a.g[i]), m, v, a, coef);
+      a.p[i] = f2bf(p); a.m[i] = f2bf(m); a.v[i] = f2bf(v);
+    }
+}
+__global__ __launch_bounds__(256) void adamw_master_guarded_kernel(MasterArgs a, const dvla_step_state* __restrict__ st) {
+  if (st->ok == 0) return;
+  a.bc2_sqrt = st->bc2_sqrt; a.step_size = st->step_size;
+  adamw_master_body(a);
+}
 
 }  // namespace
 
@@ -218,8 +335,7 @@ extern "C" int dvla_adamw_bf16(void* param, const void* grad, void* exp_avg, voi
   a.p = reinterpret_cast<bf16_t*>(param); a.g = reinterpret_cast<const bf16_t*>(grad);
   a.m = reinterpret_cast<bf16_t*>(exp_avg); a.v = reinterpret_cast<bf16_t*>(exp_avg_sq); a.n = n;
   a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-  a.inv_bc1 = (float)(1.0 / bc1); a.inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+  bf16_step_scalars(beta1, beta2, step, &a.inv_bc1, &a.inv_bc2_sqrt);
   a.sumsq = grad_sumsq; a.max_norm = max_norm;
   int64_t blocks = (n / 8 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
@@ -253,19 +369,77 @@ extern "C" int dvla_adamw_f32_master(float* param, const float* grad, float* exp
   MasterArgs a;
   a.p = param; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.sh = reinterpret_cast<bf16_t*>(shadow_bf16); a.n = n;
   // the scalars as torch/optim/adam.py (_multi_tensor_adam, capturable=False) computes them in Python floats
-  a.decay = (float)(1.0 - lr * weight_decay);
-  a.w1 = (float)(1.0 - beta1);
-  a.w1_small = fabsf(a.w1) < 0.5f;
-  a.beta2 = (float)beta2;
-  a.omb2 = (float)(1.0 - beta2);
-  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-  a.bc2_sqrt = (float)pow(bc2, 0.5);
-  a.eps = (float)eps;
-  a.step_size = (float)((lr / bc1) * -1.0);
+  master_fixed_scalars(a, lr, beta1, beta2, eps, weight_decay);
+  master_step_scalars(lr, beta1, beta2, step, &a.bc2_sqrt, &a.step_size);
   a.sumsq = grad_sumsq; a.max_norm = max_norm;
   int64_t blocks = (n / 8 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(adamw_master_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+  return dvla_check_launch();
+}
+
+// ---- guarded step (additive, ABI 9) -----------------------------------------------------------------------------------------
+extern "C" int dvla_step_candidates(double lr, double beta1, double beta2, int64_t base, int32_t n_cand, dvla_step_scalars* out) {
+  if (!out || base < 1 || n_cand < 1 || n_cand > DVLA_STEP_MAX_CANDIDATES) return DVLA_ERR_ARG;
+  for (int32_t j = 0; j < n_cand; ++j) {      // the bf16 kernel's betas are floats (dvla_adamw_bf16's arguments)
+    bf16_step_scalars((float)beta1, (float)beta2, base + j, &out[j].inv_bc1, &out[j].inv_bc2_sqrt);
+    master_step_scalars(lr, beta1, beta2, base + j, &out[j].bc2_sqrt, &out[j].step_size);
+  }
+  return DVLA_OK;
+}
+
+extern "C" int dvla_step_verdict(const float* bucket_sumsq, int32_t n, float* grad_sumsq, dvla_step_state* state,
+                                 int64_t confirmed_applied, int32_t n_cand, const dvla_step_scalars* cand, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (!bucket_sumsq || !grad_sumsq || !state || !cand || n < 0 || confirmed_applied < 0 || n_cand < 1 ||
+      n_cand > DVLA_STEP_MAX_CANDIDATES)
+    return DVLA_ERR_ARG;
+  if (n == 0) return DVLA_OK;
+  if (n > DVLA_STEP_MAX_BUCKETS || !al16(state)) return DVLA_ERR_UNSUPPORTED;
+  VerdictArgs a;
+  a.slots = bucket_sumsq; a.n = n; a.out = grad_sumsq; a.st = state; a.confirmed = confirmed_applied; a.n_cand = n_cand;
+  for (int j = 0; j < DVLA_STEP_MAX_CANDIDATES; ++j) a.c[j] = cand[j < n_cand ? j : n_cand - 1];
+  hipLaunchKernelGGL(step_verdict_kernel, dim3(1), dim3(64), 0, stream, a);
+  return dvla_check_launch();
+}
+
+extern "C" int dvla_adamw_bf16_guarded(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, float lr,
+                                       float beta1, float beta2, float eps, float weight_decay, float max_norm,
+                                       const dvla_step_state* state, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (!param || !grad || !exp_avg || !exp_avg_sq || !state || n < 0) return DVLA_ERR_ARG;
+  if (n == 0) return DVLA_OK;
+  if (!al16(param) || !al16(grad) || !al16(exp_avg) || !al16(exp_avg_sq) || !al16(state)) return DVLA_ERR_UNSUPPORTED;
+  AdamArgs a;
+  a.p = reinterpret_cast<bf16_t*>(param); a.g = reinterpret_cast<const bf16_t*>(grad);
+  a.m = reinterpret_cast<bf16_t*>(exp_avg); a.v = reinterpret_cast<bf16_t*>(exp_avg_sq); a.n = n;
+  a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay;
+  a.inv_bc1 = a.inv_bc2_sqrt = 0.f;           // the kernel takes both from the state
+  a.sumsq = max_norm > 0.f ? &state->sumsq : nullptr; a.max_norm = max_norm;
+  int64_t blocks = (n / 8 + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(adamw_guarded_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a, state);
+  return dvla_check_launch();
+}
+
+extern "C" int dvla_adamw_f32_master_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
+                                             int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay,
+                                             float max_norm, const dvla_step_state* state, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (!param || !grad || !exp_avg || !exp_avg_sq || !state || n < 0) return DVLA_ERR_ARG;
+  if (n == 0) return DVLA_OK;
+  if (!al16(param) || !al16(grad) || !al16(exp_avg) || !al16(exp_avg_sq) || (shadow_bf16 && !al16(shadow_bf16)) || !al16(state))
+    return DVLA_ERR_UNSUPPORTED;
+  MasterArgs a;
+  a.p = param; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.sh = reinterpret_cast<bf16_t*>(shadow_bf16); a.n = n;
+  master_fixed_scalars(a, lr, beta1, beta2, eps, weight_decay);
+  a.bc2_sqrt = a.step_size = 0.f;             // the kernel takes both from the state
+  a.sumsq = max_norm > 0.f ? &state->sumsq : nullptr; a.max_norm = max_norm;
+  int64_t blocks = (n / 8 + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(adamw_master_guarded_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a, state);
   return dvla_check_launch();
 }

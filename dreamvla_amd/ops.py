@@ -1010,6 +1010,14 @@ def adopt_shadow(w, sh):
     _Shadow.remember(w, sh)
 
 
+def shadow_is_current(w, sh):
+    """master `w` is served from exactly the bf16 view `sh`, recorded at w's current version, address and device (what
+    adopt_shadow(w, sh) left, if nothing has touched w through the tensor API since)"""
+    e = _Shadow.cache.get(id(w))
+    return (e is not None and e[0]() is w and e[1] == w._version and e[2] == w.data_ptr() and e[3] == w.device
+            and e[4].data_ptr() == sh.data_ptr())
+
+
 def _optimizer_maintained(e):
     """cache entry whose shadow an optimizer rewrote at the current value of its master: the shadow lies in a registered flat
     shadow buffer, the master still lives at the same offset of the matching flat master buffer, and neither its version

@@ -15,23 +15,129 @@ shadow of every master into one flat bf16 buffer per bucket.  After the step tho
 `dreamvla_amd.ops.shadow` multiplies on: the next forward issues no fp32 -> bf16 cast for a trainable weight.  A reducer
 may mix bf16 and fp32 buckets; one clip norm spans both.  With any fp32 bucket, `state_dict()` is torch.optim.AdamW's
 format (indexed in `reducer.params` order), so checkpoints move between this optimizer and the reference's loop.
+
+Guarded step (`skip_nonfinite=True`, an addition): the sums of squares go into one slot per bucket,
+`dvla_step_verdict` adds them, decides on the device whether the step is applied and picks the bias corrections of the step
+count that is then current, and `dvla_adamw_bf16_guarded` / `dvla_adamw_f32_master_guarded` do nothing on a skipped step.
 """
+import collections
+import ctypes
+import math
+import warnings
+
 import torch
 
 from . import _lib, ops
 from ._lib import check
 
 
+class _StepLedger:
+    """Host-side account of the guarded steps that are enqueued but not yet known to be applied or skipped (pure Python).
+
+    Every step ends in a readback (applied, skipped, faults, ok, sumsq -- the device's counters after that step) that completes
+    some time later.  A `ticket` stands for one readback: `ticket.done()` -> bool without blocking, `ticket.wait()` blocks until
+    it is there, `ticket.read()` returns the five values.  `begin()` retires, oldest first, every ticket that is done, which gives
+    `confirmed_applied`; the `inflight` steps behind it may each have been applied or not, so the step about to be issued finds
+    confirmed_applied + j steps applied for some j in 0 .. inflight, and `candidates()` lists the step counts
+    confirmed_applied + 1 + j its bias corrections may need.  With `window` steps in flight `begin()` waits for the oldest -- the
+    only place that blocks besides `drain()`.  A readback with faults != 0 (the device found its count outside the table it
+    was given) raises RuntimeError."""
+
+    def __init__(self, applied=0, skipped=0, window=8, on_skip=None):
+        self.window = int(window)
+        self.on_skip = on_skip              # called with the 1-based number of a step once it is confirmed skipped
+        self.reset(applied, skipped)
+
+    def reset(self, applied=0, skipped=0):
+        """forget what is in flight; the device's counters are (applied, skipped) from here on"""
+        self.confirmed_applied, self.confirmed_skipped = int(applied), int(skipped)
+        self._pending = collections.deque()
+
+    @property
+    def inflight(self):
+        return len(self._pending)
+
+    def _retire(self, ticket):
+        applied, skipped, faults, ok, _ = ticket.read()
+        if faults:
+            raise RuntimeError(f"guarded optimizer step: the device counted {int(faults)} step(s) whose applied count lay outside "
+                               f"the candidates it was given (host confirmed {self.confirmed_applied}, device {int(applied)}): "
+                               f"the optimizer state was changed behind the optimizer's back")
+        self.confirmed_applied, self.confirmed_skipped = int(applied), int(skipped)
+        if not ok and self.on_skip is not None:
+            self.on_skip(int(applied) + int(skipped))
+
+    def begin(self):
+        """start of a step: -> (confirmed_applied, number of candidates)"""
+        while self._pending and self._pending[0].done():
+            self._retire(self._pending.popleft())
+        while len(self._pending) >= self.window:
+            ticket = self._pending.popleft()
+            ticket.wait()
+            self._retire(ticket)
+        return self.confirmed_applied, len(self._pending) + 1
+
+    def candidates(self):
+        return [self.confirmed_applied + 1 + j for j in range(len(self._pending) + 1)]
+
+    def issued(self, ticket):
+        self._pending.append(ticket)
+
+    def drain(self):
+        """wait for everything in flight (blocks)"""
+        while self._pending:
+            ticket = self._pending.popleft()
+            ticket.wait()
+            self._retire(ticket)
+
+
+class _Readback:
+    """one slot of the pinned ring + the event recorded behind the copy into it (a _StepLedger ticket)"""
+
+    def __init__(self, slot):
+        self.slot = slot                                   # 32 pinned bytes: the head of dvla_step_state
+        self.event = torch.cuda.Event()
+
+    def done(self):
+        return self.event.query()
+
+    def wait(self):
+        self.event.synchronize()
+
+    def read(self):
+        i64, i32, f32 = self.slot.view(torch.int64), self.slot.view(torch.int32), self.slot.view(torch.float32)
+        return int(i64[0]), int(i64[1]), int(i64[2]), int(i32[6]), float(f32[7])
+
+
 class FlatAdamW(torch.optim.Optimizer):
     """torch.optim.Optimizer surface (param_groups with `lr` -- so torch's LR schedulers, which the reference attaches to its
     AdamW (train.py:176-200), drive it unchanged --, state_dict / load_state_dict for checkpoint / resume) over flat buffers.
     Parameters the reducer has learned never to receive a gradient (the reference's constructed-but-unused modules) are left
-    alone -- no weight decay, no moment update -- exactly as torch's AdamW skips `p.grad is None` parameters."""
+    alone -- no weight decay, no moment update -- exactly as torch's AdamW skips `p.grad is None` parameters.
+
+    skip_nonfinite=True (off by default; nothing above changes with it off): a step whose gradient holds a NaN or an inf
+    leaves every parameter, moment and shadow untouched and is counted, decided on the device with no host synchronisation.
+    The gradient norm is computed for the verdict also when max_grad_norm is None (clipping stays off).  The bias
+    corrections follow the number of APPLIED steps, so the run continues exactly as if the bad batch had not been there: an
+    applied step is the unguarded step, bit for bit.  `health()` gives the counters as device tensors,
+    `applied_steps` / `skipped_steps` as host ints (these wait for the device), `bucket_parameters(i)` names what lives in a
+    bucket; the first confirmed skip raises one RuntimeWarning (that one reads the per-bucket record back, synchronously).
+    Under data parallelism every rank steps on the same reduced buckets, so every rank reaches the same verdict without
+    talking to the others.  Not covered: a torch LR scheduler (or GradScaler) stepped on the host advances on skipped steps
+    too; the guarded step copies 32 bytes back per step and is therefore not graph-capturable; finite gradients whose norm
+    overflows fp32 are skipped as well.  With the guard on, `step_count` is the applied count last confirmed by the device
+    (it lags by up to WINDOW steps; `applied_steps` is exact)."""
+
+    WINDOW = 8      # guarded steps in flight before step() waits for the oldest readback
 
     def __init__(self, reducer, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, amsgrad=False,
-                 maximize=False):
+                 maximize=False, skip_nonfinite=False):
         if amsgrad or maximize:
             raise ValueError("FlatAdamW: amsgrad and maximize are not supported")
+        self.skip_nonfinite = bool(skip_nonfinite)
+        if self.skip_nonfinite and len(reducer.buckets) > _lib.STEP_MAX_BUCKETS:
+            raise ValueError(f"FlatAdamW(skip_nonfinite=True): at most {_lib.STEP_MAX_BUCKETS} gradient buckets "
+                             f"({len(reducer.buckets)} given)")
         self.reducer = reducer
         super().__init__(list(reducer.params), dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps),
                                                     weight_decay=float(weight_decay)))
@@ -57,6 +163,15 @@ class FlatAdamW(torch.optim.Optimizer):
         dev = reducer.buckets[0]["flat"].device
         self._sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
         self._partial = torch.empty(int(lib.dvla_sumsq_partial_len()), dtype=torch.float32, device=dev)
+        if self.skip_nonfinite:
+            self._slots = torch.zeros(len(self.flat), dtype=torch.float32, device=dev)         # one sum of squares per bucket
+            self._state = torch.zeros(ctypes.sizeof(_lib.StepState), dtype=torch.uint8, device=dev)      # dvla_step_state
+            self._cand = (_lib.StepScalars * _lib.STEP_MAX_CANDIDATES)()
+            ring = torch.zeros(self.WINDOW, _lib.STEP_READBACK_BYTES, dtype=torch.uint8).pin_memory()
+            self._ring = [_Readback(ring[i]) for i in range(self.WINDOW)]
+            self._issued = 0
+            self._skip_warned = False
+            self._ledger = _StepLedger(window=self.WINDOW, on_skip=self._on_skip)
 
     def _ranges(self, bi):
         """element ranges of bucket bi that hold parameters which receive gradients (maximal runs; alignment gaps between two
@@ -90,7 +205,113 @@ class FlatAdamW(torch.optim.Optimizer):
         return b["expected"]
 
     @torch.no_grad()
+    def _guarded_step(self):
+        lib = _lib.load()
+        stream = torch.cuda.current_stream().cuda_stream
+        grp = self.param_groups[0]
+        lr, (b1, b2), eps, wd = float(grp["lr"]), grp["betas"], float(grp["eps"]), float(grp["weight_decay"])
+        max_norm = self.max_grad_norm if self.max_grad_norm is not None else 0.0        # <= 0: the norm only feeds the verdict
+        confirmed, n_cand = self._ledger.begin()
+        self.step_count = confirmed
+        for i, s in enumerate(self.flat):
+            fn = lib.dvla_sumsq_f32 if "sh" in s else lib.dvla_sumsq_bf16
+            check(fn(s["g"].data_ptr(), s["g"].numel(), self._partial.data_ptr(), self._slots.data_ptr() + 4 * i, 0, stream),
+                  "dvla_sumsq")
+        check(lib.dvla_step_candidates(lr, float(b1), float(b2), confirmed + 1, n_cand, self._cand), "dvla_step_candidates")
+        state = self._state.data_ptr()
+        check(lib.dvla_step_verdict(self._slots.data_ptr(), len(self.flat), self._sumsq.data_ptr(), state, confirmed, n_cand,
+                                    self._cand, stream), "dvla_step_verdict")
+        for bi, s in enumerate(self.flat):
+            for (lo, hi) in self._ranges(bi):
+                if hi <= lo:
+                    continue
+                if "sh" in s:
+                    o = 4 * lo
+                    check(lib.dvla_adamw_f32_master_guarded(s["p"].data_ptr() + o, s["g"].data_ptr() + o, s["m"].data_ptr() + o,
+                                                            s["v"].data_ptr() + o, s["sh"].data_ptr() + 2 * lo, hi - lo, lr,
+                                                            float(b1), float(b2), eps, wd, max_norm, state, stream),
+                          "dvla_adamw_f32_master_guarded")
+                    continue
+                o = 2 * lo
+                check(lib.dvla_adamw_bf16_guarded(s["p"].data_ptr() + o, s["g"].data_ptr() + o, s["m"].data_ptr() + o,
+                                                  s["v"].data_ptr() + o, hi - lo, lr, float(b1), float(b2), eps, wd, max_norm,
+                                                  state, stream), "dvla_adamw_bf16_guarded")
+        ticket = self._ring[self._issued % self.WINDOW]       # free: fewer than WINDOW steps are in flight after begin()
+        self._issued += 1
+        ticket.slot.copy_(self._state[:_lib.STEP_READBACK_BYTES], non_blocking=True)
+        ticket.event.record(torch.cuda.current_stream())
+        self._ledger.issued(ticket)
+        if self.master_mode:
+            self._publish_shadows_guarded()
+
+    def _on_skip(self, step):
+        if self._skip_warned:
+            return
+        self._skip_warned = True
+        # one synchronous read of the device's latch: the number of the LAST skipped step and its per-bucket sums, which belong
+        # together (the step just confirmed may be an earlier one)
+        tail = self._state.cpu()
+        last = int(tail[_lib.StepState.latched_step.offset:][:8].view(torch.int64)[0])
+        sums = tail[_lib.StepState.skipped_bucket_sumsq.offset:][:4 * len(self.flat)].view(torch.float32).tolist()
+        bad = [i for i, x in enumerate(sums) if not math.isfinite(x)]
+        where = f"non-finite gradient in bucket(s) {bad}" if bad else "the gradient norm overflows fp32"
+        first = "" if last == step else f" (the first confirmed skip was step {step})"
+        warnings.warn(f"FlatAdamW: step {last} was skipped: {where}{first}; see bucket_parameters().  Further skips are counted "
+                      f"in health() / skipped_steps without a warning.", RuntimeWarning, stacklevel=3)
+
+    def _state_view(self, field, dtype):
+        f = getattr(_lib.StepState, field)
+        return self._state[f.offset:f.offset + f.size].view(dtype)
+
+    def _require_guard(self, what):
+        if not self.skip_nonfinite:
+            raise RuntimeError(f"FlatAdamW.{what}: construct the optimizer with skip_nonfinite=True")
+
+    def health(self):
+        """the guard's account as device tensors (copies enqueued on the current stream, no synchronisation): steps applied and
+        skipped, the last step's verdict (1 applied / 0 skipped) and gradient norm, and the 1-based number and per-bucket gradient
+        norms of the last skipped step (bucket_parameters(i) says what lives in bucket i)"""
+        self._require_guard("health()")
+        return {"applied": self._state_view("applied", torch.int64)[0].clone(),
+                "skipped": self._state_view("skipped", torch.int64)[0].clone(),
+                "last_ok": self._state_view("ok", torch.int32)[0].clone(),
+                "last_grad_norm": self._state_view("sumsq", torch.float32)[0].sqrt(),
+                "last_skipped_step": self._state_view("latched_step", torch.int64)[0].clone(),
+                "skipped_bucket_norms": self._state_view("skipped_bucket_sumsq", torch.float32)[:len(self.flat)].sqrt()}
+
+    def bucket_parameters(self, i):
+        """indices into reducer.params of the parameters in gradient bucket i"""
+        index = {id(p): k for k, p in enumerate(self.reducer.params)}
+        return [index[id(p)] for p in self.reducer.buckets[i]["params"]]
+
+    @property
+    def applied_steps(self):
+        """steps applied so far (host int).  Waits for every enqueued step: a synchronisation."""
+        self._require_guard("applied_steps")
+        self._ledger.drain()
+        self.step_count = self._ledger.confirmed_applied
+        return self._ledger.confirmed_applied
+
+    @property
+    def skipped_steps(self):
+        """steps skipped so far (host int).  Waits for every enqueued step: a synchronisation."""
+        self._require_guard("skipped_steps")
+        self._ledger.drain()
+        return self._ledger.confirmed_skipped
+
+    def _reset_guard(self, applied, skipped):
+        """device state and ledger to a resumed run's counts (ordered behind whatever is enqueued on the current stream)"""
+        head = torch.zeros(self._state.numel(), dtype=torch.uint8)
+        head[:16].view(torch.int64).copy_(torch.tensor([int(applied), int(skipped)], dtype=torch.int64))
+        self._state.copy_(head)
+        torch.cuda.current_stream().synchronize()          # the readbacks still in flight are forgotten with the ledger
+        self._ledger.reset(applied, skipped)
+        self.step_count = int(applied)
+
+    @torch.no_grad()
     def step(self, closure=None):
+        if self.skip_nonfinite:
+            return self._guarded_step()
         lib = _lib.load()
         stream = torch.cuda.current_stream().cuda_stream
         self.step_count += 1
@@ -133,6 +354,23 @@ class FlatAdamW(torch.optim.Optimizer):
                 if used:
                     ops.adopt_shadow(p, s["sh"][off:off + p.numel()].view(p.shape))
 
+    def _publish_shadows_guarded(self):
+        """_publish_shadows after a guarded step, which may not have written the copies: a bucket in which some stepped master
+        is not already served from this flat shadow at its current version -- the first step, or masters rewritten since (a
+        checkpoint load) -- first gets its whole shadow cast anew from the masters, so the copies are current whether or not
+        the step was applied.  In the steady state that is no launch."""
+        for bi, s in enumerate(self.flat):
+            if "sh" not in s:
+                continue
+            b = self.reducer.buckets[bi]
+            views = [(p, s["sh"][off:off + p.numel()].view(p.shape))
+                     for p, off, used in zip(b["params"], b["offsets"], self._stepped(bi)) if used]
+            if not all(ops.shadow_is_current(p, sh) for p, sh in views):
+                check(_lib.load().dvla_cast_f32_to_bf16(s["p"].data_ptr(), s["sh"].data_ptr(), s["p"].numel(),
+                                                        torch.cuda.current_stream().cuda_stream), "dvla_cast_f32_to_bf16")
+            for p, sh in views:
+                ops.adopt_shadow(p, sh)
+
     def zero_grad(self, set_to_none=True):
         self.reducer.zero_grad()
 
@@ -145,18 +383,35 @@ class FlatAdamW(torch.optim.Optimizer):
 
     def state_dict(self):
         """master mode: torch.optim.AdamW's format (see torch_state_from_flat).  bf16 buckets only: step count, hyper-parameters
-        and both moments (flat, per bucket) + the layout they belong to"""
+        and both moments (flat, per bucket) + the layout they belong to.  With skip_nonfinite the stored step is the number of
+        APPLIED steps (this waits for every enqueued step) and param_groups[0]["skipped_steps"] is added."""
+        if self.skip_nonfinite:
+            sd = self._state_dict(self.applied_steps)
+            sd["param_groups"][0]["skipped_steps"] = self._ledger.confirmed_skipped
+            return sd
+        return self._state_dict(self.step_count)
+
+    def _state_dict(self, step):
         if self.master_mode:
-            with_state = [[bool(u) and self.step_count > 0 for u in self._stepped(bi)] for bi in range(len(self.flat))]
+            with_state = [[bool(u) and step > 0 for u in self._stepped(bi)] for bi in range(len(self.flat))]
             return {"state": torch_state_from_flat(self._layout(), [s["m"] for s in self.flat], [s["v"] for s in self.flat],
-                                                   self.step_count, with_state),
+                                                   step, with_state),
                     "param_groups": [_torch_group(g, len(self.reducer.params)) for g in self.param_groups]}
-        return {"step": self.step_count,
+        return {"step": step,
                 "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups],
                 "layout": [[int(p.numel()) for p in b["params"]] for b in self.reducer.buckets],
                 "exp_avg": [s["m"].clone() for s in self.flat], "exp_avg_sq": [s["v"].clone() for s in self.flat]}
 
     def load_state_dict(self, sd):
+        """the inverse of state_dict().  With skip_nonfinite the device's counters and the ledger restart from the loaded step
+        (as the applied count) and the dict's "skipped_steps" (0 if it has none); without it that key is ignored."""
+        self._load_state_dict(sd)
+        skipped = int(self.param_groups[0].pop("skipped_steps", 0) if not self.master_mode
+                      else sd["param_groups"][0].get("skipped_steps", 0))
+        if self.skip_nonfinite:
+            self._reset_guard(self.step_count, skipped)
+
+    def _load_state_dict(self, sd):
         if self.master_mode:
             groups = sd.get("param_groups") if isinstance(sd, dict) else None
             n = len(self.reducer.params)

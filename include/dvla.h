@@ -369,6 +369,57 @@ int dvla_sumsq_f32(const float* x, int64_t n, float* partial, float* out, int32_
 int dvla_adamw_f32_master(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, int64_t n,
                           double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
                           const float* grad_sumsq, float max_norm, void* stream);
+/* (additive, ABI 9) The guarded step: the same two AdamW kernels under a verdict taken on the device, so that a step whose
+ * gradient is not finite changes nothing and is counted, with no host synchronisation.  The bias corrections
+ * depend on the number of steps APPLIED so far, which the host -- running ahead of the device -- does not know; it keeps
+ * deriving them in doubles (dvla_step_candidates, the expressions of dvla_adamw_bf16 / dvla_adamw_f32_master) for every count
+ * that is still possible and hands the table to dvla_step_verdict by value; the device picks the row.
+ * dvla_step_scalars: what depends on the step count -- inv_bc1 = 1 / (1 - beta1^t) and inv_bc2_sqrt = 1 / sqrt(1 - beta2^t)
+ *   (dvla_adamw_bf16's kernel), bc2_sqrt = sqrt(1 - beta2^t) and step_size = -lr / (1 - beta1^t) (dvla_adamw_f32_master's).
+ * dvla_step_state: device memory, 16-byte aligned, zeroed once by the caller (or set to a resumed run's counts).  The first
+ *   32 bytes are what a caller reads back per step: the counters, the verdict and the norm.
+ *     applied / skipped: steps applied / skipped so far.  faults: steps whose applied count lay outside the caller's table (the
+ *     caller lost track; such a step is skipped too, and the caller must treat faults != 0 as an error).
+ *     ok: the current step's verdict.  sumsq: its total sum of squares (what *grad_sumsq receives).
+ *     cand: the row chosen, and the row itself (inv_bc1 ... step_size).
+ *     skipped_bucket_sumsq[0 .. n_latched): the per-bucket sums of the LAST skipped step (which bucket went non-finite), and
+ *     latched_step: that step's 1-based number (applied + skipped after it).
+ *   At most DVLA_STEP_MAX_BUCKETS buckets (more: DVLA_ERR_UNSUPPORTED), at most DVLA_STEP_MAX_CANDIDATES rows.
+ * dvla_step_candidates: no launch.  out[j], j < n_cand, = the scalars of step count base + j (base >= 1) from the double
+ *   hyper-parameters; the bf16 pair from the betas rounded to float, as dvla_adamw_bf16 receives them.
+ * dvla_step_verdict: one launch of one wave.  bucket_sumsq[i], i < n, is bucket i's sum of squares (dvla_sumsq_bf16 /
+ *   dvla_sumsq_f32 with accumulate = 0 into slot i).  The slots are added in index order -- the order of the `accumulate` chain,
+ *   so the total has the same bits -- and written to *grad_sumsq and state->sumsq; ok = the total is finite (one non-finite
+ *   element, or a norm that overflows fp32, makes it not).  j = state->applied - confirmed_applied selects cand[j] (a HOST
+ *   table, copied into the kernel arguments); j outside [0, n_cand) forces ok = 0 and counts a fault.  Then applied += ok,
+ *   skipped += !ok, and a skipped step latches its slots.
+ * dvla_adamw_bf16_guarded / dvla_adamw_f32_master_guarded: their twins without `step` and `grad_sumsq` -- both come from the
+ *   state (one uniform load per workgroup).  state->ok == 0: the kernel returns before it reads or writes param, exp_avg,
+ *   exp_avg_sq or the shadow.  Otherwise each element goes through the twin's own element function: bit-identical results
+ *   for the same scalars.  max_norm <= 0: no clipping.
+ * DVLA_ERR_ARG: a null pointer, a negative size or count, base < 1, n_cand outside 1 .. DVLA_STEP_MAX_CANDIDATES.
+ * DVLA_ERR_UNSUPPORTED: a base that is not 16-byte aligned, n > DVLA_STEP_MAX_BUCKETS.  n == 0: DVLA_OK, nothing launched. */
+#define DVLA_STEP_MAX_BUCKETS 256
+#define DVLA_STEP_MAX_CANDIDATES 9
+typedef struct dvla_step_scalars { float inv_bc1, inv_bc2_sqrt, bc2_sqrt, step_size; } dvla_step_scalars;
+typedef struct dvla_step_state {
+  int64_t applied, skipped, faults;
+  int32_t ok;
+  float sumsq;
+  int32_t cand, n_latched;
+  float inv_bc1, inv_bc2_sqrt, bc2_sqrt, step_size;
+  int64_t latched_step;
+  float skipped_bucket_sumsq[DVLA_STEP_MAX_BUCKETS];
+} __attribute__((aligned(16))) dvla_step_state;
+int dvla_step_candidates(double lr, double beta1, double beta2, int64_t base, int32_t n_cand, dvla_step_scalars* out);
+int dvla_step_verdict(const float* bucket_sumsq, int32_t n, float* grad_sumsq, dvla_step_state* state,
+                      int64_t confirmed_applied, int32_t n_cand, const dvla_step_scalars* cand, void* stream);
+int dvla_adamw_bf16_guarded(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, float lr, float beta1,
+                            float beta2, float eps, float weight_decay, float max_norm, const dvla_step_state* state,
+                            void* stream);
+int dvla_adamw_f32_master_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
+                                  int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay,
+                                  float max_norm, const dvla_step_state* state, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Token assembly (models/dreamvla_model.py:739-759): out[b, s, t, :] = part_k[b, s, t - tok_begin_k, :] + pos[s, :]
