@@ -43,7 +43,6 @@ __device__ __forceinline__ float add_mul_rn(float x, float a, float b) {
 
 // ---- fast transcendental helpers (epilogue-resident: they must cost a handful of VALU ops, not a libm call) ----
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }            // v_rcp_f32 (1 ulp)
-__device__ __forceinline__ float fast_exp(float x) { return fast_exp2(x * 1.4426950408889634f); }  // e^x
 // Activations.  The GEMM epilogue runs them on PAIRS (f32x2) so that the polynomial parts issue as packed fp32
 // (v_pk_fma_f32 / v_pk_mul_f32: two values per lane and instruction); the scalar forms wrap the pair forms.
 //   Phi(x) = 0.5 (1 + erf(x / sqrt 2)) by Abramowitz-Stegun 7.1.26 in its erfc form:
@@ -230,11 +229,6 @@ __device__ __forceinline__ uint32_t drop_elem(uint32_t x, uint32_t tk, uint32_t 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
 

@@ -143,19 +143,17 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ ws, void* C, int6
   }
 }
 
-int g_gemm_variant = -1;   // 0 auto; force: 2 register-staged, 4 / 6 / 7 ring 256^2 / 128^2 / 256x128 BK 64, 8 / 9 / 10 phase (plain / stream-K
-                           // hybrid / full), 11 few-rows; any other number, or a configuration that does not take the problem: register-staged
+int g_gemm_variant = -1;   // a DVLA_GEMM_CFG_* of dvla.h (AUTO: the cost model below; any other number, or a configuration that does not
+                           // take the problem: the register-staged kernel); < 0: DVLA_GEMM_VARIANT not read yet
 inline int gemm_variant() {
   if (g_gemm_variant < 0) {
     const char* e = getenv("DVLA_GEMM_VARIANT");
-    g_gemm_variant = e ? atoi(e) : 0;
+    g_gemm_variant = e ? atoi(e) : DVLA_GEMM_CFG_AUTO;
   }
   return g_gemm_variant;
 }
 
-
 inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 
 // tile counts of a configuration + the reciprocals ring_item decodes with (d == 1: 2^32 - 1, the correction makes it exact)
 template <int BM, int BN, int GH>
@@ -167,53 +165,44 @@ void set_tiles(GemmKArgs& a) {
   a.inv_per_panel = inv((int64_t)GH * a.tiles_n);
 }
 
-template <class CF>
-void launch_cfg(GemmKArgs& a, int combo, int split_k, hipStream_t stream) {
-  a.tiles_m = (int)((a.M + CF::BM - 1) / CF::BM);
-  a.tiles_n = (int)((a.N + CF::BN - 1) / CF::BN);
+// run-time operand layout (combo = 2 a_trans + b_trans) / epilogue class -> compile-time constants: f is a generic lambda that
+// names the instance with them.  The instances are `extern template` (above): one that gemm_inst_list.h lacks fails at link time.
+template <class F>
+void with_layout(int combo, F&& f) {
   switch (combo) {
-    case 0: launch_one<CF, false, false>(a, split_k, stream); break;
-    case 1: launch_one<CF, false, true>(a, split_k, stream); break;
-    case 2: launch_one<CF, true, false>(a, split_k, stream); break;
-    default: launch_one<CF, true, true>(a, split_k, stream); break;
+    case 0: f(std::bool_constant<false>{}, std::bool_constant<false>{}); break;
+    case 1: f(std::bool_constant<false>{}, std::bool_constant<true>{}); break;
+    case 2: f(std::bool_constant<true>{}, std::bool_constant<false>{}); break;
+    default: f(std::bool_constant<true>{}, std::bool_constant<true>{}); break;
+  }
+}
+template <class F>
+void with_epi(int epi, F&& f) {
+  switch (epi) {
+    case EPI_P0: f(std::integral_constant<int, EPI_P0>{}); break;
+    case EPI_P_ERF: f(std::integral_constant<int, EPI_P_ERF>{}); break;
+    case EPI_P_TANH: f(std::integral_constant<int, EPI_P_TANH>{}); break;
+    case EPI_A0: f(std::integral_constant<int, EPI_A0>{}); break;
+    case EPI_A_ERF: f(std::integral_constant<int, EPI_A_ERF>{}); break;
+    case EPI_A_TANH: f(std::integral_constant<int, EPI_A_TANH>{}); break;
+    case EPI_F32: f(std::integral_constant<int, EPI_F32>{}); break;
+    default: f(std::integral_constant<int, EPI_GEN>{}); break;
   }
 }
 
-template <class RC, bool AT, bool BT>
-void launch_ring_epi(const GemmKArgs& a, int split_k, hipStream_t stream) {
-  switch (epi_class(a)) {
-    case EPI_P0: launch_ring_one<RC, AT, BT, EPI_P0>(a, split_k, stream); break;
-    case EPI_P_ERF: launch_ring_one<RC, AT, BT, EPI_P_ERF>(a, split_k, stream); break;
-    case EPI_P_TANH: launch_ring_one<RC, AT, BT, EPI_P_TANH>(a, split_k, stream); break;
-    case EPI_A0: launch_ring_one<RC, AT, BT, EPI_A0>(a, split_k, stream); break;
-    case EPI_A_ERF: launch_ring_one<RC, AT, BT, EPI_A_ERF>(a, split_k, stream); break;
-    case EPI_A_TANH: launch_ring_one<RC, AT, BT, EPI_A_TANH>(a, split_k, stream); break;
-    case EPI_F32: launch_ring_one<RC, AT, BT, EPI_F32>(a, split_k, stream); break;
-    default: launch_ring_one<RC, AT, BT, EPI_GEN>(a, split_k, stream); break;
-  }
+void launch_reg(GemmKArgs& a, int combo, int split_k, hipStream_t stream) {
+  a.tiles_m = (int)((a.M + CfgS::BM - 1) / CfgS::BM);
+  a.tiles_n = (int)((a.N + CfgS::BN - 1) / CfgS::BN);
+  with_layout(combo, [&](auto at, auto bt) { launch_one<CfgS, decltype(at)::value, decltype(bt)::value>(a, split_k, stream); });
 }
 template <class RC>
-void launch_ring(GemmKArgs& a, int combo, int split_k, hipStream_t stream) {
+void launch_ring(GemmKArgs& a, int combo, int split_k, hipStream_t stream, int /*stream_k*/) {
   set_tiles<RC::BM, RC::BN, RC::GH>(a);
-  switch (combo) {
-    case 0: launch_ring_epi<RC, false, false>(a, split_k, stream); break;
-    case 1: launch_ring_epi<RC, false, true>(a, split_k, stream); break;
-    case 2: launch_ring_epi<RC, true, false>(a, split_k, stream); break;
-    default: launch_ring_epi<RC, true, true>(a, split_k, stream); break;
-  }
-}
-template <bool AT, bool BT>
-void launch_phase_epi(const GemmKArgs& a, int split_k, hipStream_t stream) {
-  switch (epi_class(a)) {
-    case EPI_P0: launch_phase_one<AT, BT, EPI_P0, 0>(a, split_k, stream); break;
-    case EPI_P_ERF: launch_phase_one<AT, BT, EPI_P_ERF, 0>(a, split_k, stream); break;
-    case EPI_P_TANH: launch_phase_one<AT, BT, EPI_P_TANH, 0>(a, split_k, stream); break;
-    case EPI_A0: launch_phase_one<AT, BT, EPI_A0, 0>(a, split_k, stream); break;
-    case EPI_A_ERF: launch_phase_one<AT, BT, EPI_A_ERF, 0>(a, split_k, stream); break;
-    case EPI_A_TANH: launch_phase_one<AT, BT, EPI_A_TANH, 0>(a, split_k, stream); break;
-    case EPI_F32: launch_phase_one<AT, BT, EPI_F32, 0>(a, split_k, stream); break;
-    default: launch_phase_one<AT, BT, EPI_GEN, 0>(a, split_k, stream); break;
-  }
+  with_layout(combo, [&](auto at, auto bt) {
+    with_epi(epi_class(a), [&](auto epi) {
+      launch_ring_one<RC, decltype(at)::value, decltype(bt)::value, decltype(epi)::value>(a, split_k, stream);
+    });
+  });
 }
 // ---- stream-K scratch: one 256-KiB fp32 slab and one flag per workgroup, per (device, stream); allocated on first use
 // (never while the stream is being captured: such launches take the plain schedule), kept for the life of the process.
@@ -262,7 +251,7 @@ inline int streamk_tiles(int64_t tiles, int cus, bool full = false) {
   return (int)(st - dp_rounds * groups);
 }
 // stream_k: 0 = plain schedule, 1 = hybrid (partial rounds only), 2 = full
-void launch_phase(GemmKArgs& a, int combo, int split_k, hipStream_t stream, int stream_k = 0) {
+void launch_phase(GemmKArgs& a, int combo, int split_k, hipStream_t stream, int stream_k) {
   set_tiles<PCfg::BM, PCfg::BN, PCfg::GH>(a);
   a.sk_tiles = 0;
   if (a.K % PCfg::BKS != 0) {       // partial last K-tile (phase_tail): its own instantiation, plain schedule
@@ -279,12 +268,11 @@ void launch_phase(GemmKArgs& a, int combo, int split_k, hipStream_t stream, int 
     const int r = streamk_tiles((int64_t)a.tiles_m * a.tiles_n, groups, stream_k == 2);
     if (r > 0 && sk_scratch(stream, groups, &a.sk_slabs, &a.sk_flags)) a.sk_tiles = r;
   }
-  switch (combo) {
-    case 0: launch_phase_epi<false, false>(a, split_k, stream); break;
-    case 1: launch_phase_epi<false, true>(a, split_k, stream); break;
-    case 2: launch_phase_epi<true, false>(a, split_k, stream); break;
-    default: launch_phase_epi<true, true>(a, split_k, stream); break;
-  }
+  with_layout(combo, [&](auto at, auto bt) {
+    with_epi(epi_class(a), [&](auto epi) {
+      launch_phase_one<decltype(at)::value, decltype(bt)::value, decltype(epi)::value, 0>(a, split_k, stream);
+    });
+  });
 }
 template <class RC>
 bool ring_ok(const GemmKArgs& a, int combo) {
@@ -330,19 +318,72 @@ bool phase_ok(const GemmKArgs& a, int combo) {
   return a_rows * a.lda * 2 < (1ll << 32) && b_rows * a.ldb * 2 < (1ll << 32);
 }
 
-// fraction of workgroup slots kept busy when `tiles` workgroups run `slots` at a time
-inline double fill(int64_t tiles, int64_t slots) {
-  const int64_t rounds = (tiles + slots - 1) / slots;
-  return (double)tiles / (double)(rounds * slots);
+// ---- the tiled DMA configurations, in the order the cost model considers them (ties go to the earlier row).  A new
+// configuration is one row here and its lines in gemm_inst_list.h.
+// Cost model: T = rounds * (fixed_us + stage_us * ns), rounds = ceil(work items / workgroup slots), ns = 32-wide K stages per
+// item.  Constants in microseconds per round, measured on MI355X with tests/probes/gemm_probe.cpp (K sweep at 20832 x 4096, plain
+// epilogue, round 2: profiles/r02_gemm_probe_final.txt): with the register-only epilogue the fixed cost per round is 2.9 / 3.6 /
+// 5.8 / 6.6 us for 128^2 / 256x128 BK64 / 256^2 / phase (it was 5.7 / 5.9 / 18.7 with the LDS-patch epilogue of round 1), the slope
+// per stage 0.58 / 0.49 / 0.85 / 0.775.  The online tuner (dreamvla_amd.ops.GemmTuner) refines this per problem key in-model.
+// streamk_us: the stream-K hybrid of the same kernel runs fractional rounds, plus one slab write + one slab read per workgroup and
+// the less regular operand reuse of the shared round (~18 us measured over the plain schedule at equal round counts); 0 = the
+// configuration has no stream-K schedule (ids 9 / 10 are the phase row with launch's stream_k = 1 / 2).
+// ksum_combos: the layouts (bit `combo`) whose fp32-class instances carry the k-sum code -- every one of a ring kernel, the TT
+// layout (every weight gradient) of the phase kernel; ksum_share: tiles of a tile row (A sums) / tile column (B sums) that share
+// a sum, each with its own KSUM_PARTS partial rows.
+constexpr int PHASE_KSUM_SHARE = 4;
+struct TiledCfg {
+  int id;                         // DVLA_GEMM_CFG_*
+  int bm, bn, wg_per_cu;
+  double fixed_us, stage_us, streamk_us;
+  int ksum_combos, ksum_share;
+  bool (*admits)(const GemmKArgs&, int combo);
+  void (*launch)(GemmKArgs&, int combo, int split_k, hipStream_t, int stream_k);
+};
+template <class RC>
+constexpr TiledCfg ring_row(int id, double fixed_us, double stage_us) {
+  return {id, RC::BM, RC::BN, RC::WG_PER_CU, fixed_us, stage_us, 0.0, 0xf, 1, ring_ok<RC>, launch_ring<RC>};
+}
+const TiledCfg TILED[] = {
+    ring_row<RCfgS>(DVLA_GEMM_CFG_RING_128, 2.9, 0.58),
+    ring_row<RCfgM64>(DVLA_GEMM_CFG_RING_256X128, 3.6, 0.49),
+    ring_row<RCfgL>(DVLA_GEMM_CFG_RING_256, 5.8, 0.85),
+    {DVLA_GEMM_CFG_PHASE, PCfg::BM, PCfg::BN, PCfg::WG_PER_CU, 6.6, 0.775, 18.0, 1 << 3, PHASE_KSUM_SHARE, phase_ok, launch_phase},
+};
+constexpr double MODEL_STAGE_K = 32.0;
+// the row a call runs on (null: none) and its schedule: the cheapest that admits the problem, or the forced one if it does
+const TiledCfg* choose_tiled(const GemmKArgs& a, int combo, int variant, int* stream_k) {
+  const TiledCfg* cfg = nullptr;
+  if (variant == DVLA_GEMM_CFG_AUTO) {
+    const double ns = (double)(a.k_per_split < a.K ? a.k_per_split : a.K) / MODEL_STAGE_K;
+    const int slots = num_cus();
+    double best = 1e30;
+    for (const TiledCfg& c : TILED) {
+      if (!c.admits(a, combo)) continue;
+      const int64_t tiles = ((a.M + c.bm - 1) / c.bm) * ((a.N + c.bn - 1) / c.bn), items = tiles * a.split_k;
+      const int64_t rounds = (items + (int64_t)slots * c.wg_per_cu - 1) / ((int64_t)slots * c.wg_per_cu);
+      const double t = (double)rounds * (c.fixed_us + c.stage_us * ns);
+      if (t < best) { best = t; cfg = &c; *stream_k = 0; }
+      if (c.streamk_us > 0.0 && a.split_k == 1 && streamk_enabled() && streamk_tiles(tiles, slots) > 0) {
+        const double tk = (double)tiles / slots * (c.fixed_us + c.stage_us * ns) + c.streamk_us;
+        if (tk < best) { best = tk; cfg = &c; *stream_k = 1; }
+      }
+    }
+  } else {
+    const bool sk = variant == DVLA_GEMM_CFG_PHASE_STREAMK, sk_full = variant == DVLA_GEMM_CFG_PHASE_STREAMK_FULL;
+    const int id = (sk || sk_full) ? DVLA_GEMM_CFG_PHASE : variant;
+    for (const TiledCfg& c : TILED)
+      if (c.id == id && c.admits(a, combo)) { cfg = &c; *stream_k = sk ? 1 : sk_full ? 2 : 0; }
+  }
+  return cfg;
 }
 
 }  // namespace
 
 // what the last dvla_gemm_bf16 call of this process actually launched (tests assert that a forced configuration ran and did
-// not fall back): 2 register-staged, 4 / 6 / 7 ring 256^2 / 128^2 / 256x128, 8 phase (plain schedule), 9 / 10 phase with the
-// stream-K hybrid / full schedule ENGAGED (a stream-K request that does not apply reports 8); 0 = nothing launched yet
-// 89 (only in a build with -DDVLA_GEMM_STAMPS): the phase kernel's s_memtime build, NN layout, plain bf16 epilogue
-// (tests/probes/gemm_probe.cpp --stamps)
+// not fall back), a DVLA_GEMM_CFG_* of dvla.h: the stream-K ids only with the schedule ENGAGED (a stream-K request that does not
+// apply reports PHASE); 0 = nothing launched yet.  PHASE_STAMPS (only in a build with -DDVLA_GEMM_STAMPS): the phase kernel's
+// s_memtime build, NN layout, plain bf16 epilogue (tests/probes/gemm_probe.cpp --stamps)
 static int g_last_variant = 0;
 extern "C" int dvla_last_gemm_variant(void) { return g_last_variant; }
 extern "C" void dvla_set_gemm_variant(int v) { g_gemm_variant = v; }
@@ -357,8 +398,8 @@ extern "C" void dvla_get_gemm_schedule(int* oversubscribe, int* stream_k) {
 }
 
 extern "C" int64_t dvla_gemm_ksum_partial_rows(int32_t split_k) {
-  // (x 4: the phase kernel spreads a row's sum over up to four tiles, each with its own KSUM_PARTS partial rows)
-  const int64_t fused = (int64_t)(split_k > 1 ? split_k : 1) * dvla_gemm::KSUM_PARTS * 4, fallback = dvla_colsum_partial_rows();
+  // (x PHASE_KSUM_SHARE: the phase kernel spreads a row's sum over up to four tiles, each with its own KSUM_PARTS partial rows)
+  const int64_t fused = (int64_t)(split_k > 1 ? split_k : 1) * dvla_gemm::KSUM_PARTS * PHASE_KSUM_SHARE, fallback = dvla_colsum_partial_rows();
   return fused > fallback ? fused : fallback;
 }
 
@@ -428,82 +469,37 @@ extern "C" int dvla_gemm_bf16(const dvla_gemm_params* q, void* stream_) {
   if (split_k > 1 && ((q->N & 3) != 0 || !aligned(q->workspace, 16))) a.epi_vec = 0;
 
   const int combo = (q->a_trans ? 2 : 0) | (q->b_trans ? 1 : 0);
-  int variant = gemm_variant();
-  {
-    // Configuration choice: cheapest by a two-constant model per configuration, T = rounds * (fixed + stage * ns),
-    // rounds = ceil(work items / workgroup slots), ns = 32-wide K stages per item.  Constants in microseconds per round,
-    // measured on MI355X with tests/probes/gemm_probe.cpp (K sweep at 20832 x 4096, plain epilogue, round 2:
-    // profiles/r02_gemm_probe_final.txt): with the register-only epilogue the fixed cost per round is 2.9 / 3.6 / 5.8 / 6.6 us
-    // for 128^2 / 256x128 BK64 / 256^2 / phase (it was 5.7 / 5.9 / 18.7 with the LDS-patch epilogue of round 1), the slope per
-    // stage 0.58 / 0.49 / 0.85 / 0.775.  The online tuner (dreamvla_amd.ops.GemmTuner) refines this per problem key in-model.
-    // The register-staged kernel is the fallback for shapes the DMA kernels do not take (ragged N, unaligned operands, tiny).
-    int choice = 0;   // 0 = register-staged S (always valid), 1 = ring L, 3 = ring S, 4 = ring M64, 5 = phase, 11 = skinny
-    if (a.a_ln && !(skinny_ok(a, combo, split_k) && skinny_ln_ok(a))) return DVLA_ERR_UNSUPPORTED;   // only the few-rows kernel normalises
-    if ((variant == 0 || variant == 11 || a.a_ln) && skinny_ok(a, combo, split_k)) {
-      choice = 11;      // few rows (evaluation-time shapes): one 32 x 32 tile per workgroup, K split over its four waves
-    } else if (variant == 0) {
-      const double ns = (double)(a.k_per_split < a.K ? a.k_per_split : a.K) / 32.0;
-      const int slots = num_cus();
-      double best = 1e30;
-      auto consider = [&](int c, int64_t bm, int64_t bn, int wg_per_cu, double fixed_us, double stage_us) {
-        const int64_t items = ((q->M + bm - 1) / bm) * ((q->N + bn - 1) / bn) * split_k;
-        const int64_t rounds = (items + (int64_t)slots * wg_per_cu - 1) / ((int64_t)slots * wg_per_cu);
-        const double t = (double)rounds * (fixed_us + stage_us * ns);
-        if (t < best) { best = t; choice = c; }
-      };
-      if (ring_ok<RCfgS>(a, combo)) consider(3, 128, 128, 2, 2.9, 0.58);
-      if (ring_ok<RCfgM64>(a, combo)) consider(4, 256, 128, 1, 3.6, 0.49);
-      if (ring_ok<RCfgL>(a, combo)) consider(1, 256, 256, 1, 5.8, 0.85);
-      if (phase_ok(a, combo)) {
-        consider(5, 256, 256, 1, 6.6, 0.775);
-        // stream-K hybrid of the same kernel: fractional rounds, plus one slab write + one slab read per workgroup and the
-        // less regular operand reuse of the shared round (~18 us measured over the plain schedule at equal round counts)
-        const int64_t tiles = ((q->M + 255) / 256) * ((q->N + 255) / 256);
-        if (split_k == 1 && streamk_enabled() && streamk_tiles(tiles, slots) > 0) {
-          const double t = (double)tiles / slots * (6.6 + 0.775 * ns) + 18.0;
-          if (t < best) { best = t; choice = 6; }
-        }
-      }
-    } else if (variant == 4 && ring_ok<RCfgL>(a, combo)) choice = 1;
-    else if (variant == 6 && ring_ok<RCfgS>(a, combo)) choice = 3;
-    else if (variant == 7 && ring_ok<RCfgM64>(a, combo)) choice = 4;
-    else if (variant == 8 && phase_ok(a, combo)) choice = 5;
-    else if (variant == 9 && phase_ok(a, combo)) choice = 6;
-    else if (variant == 10 && phase_ok(a, combo)) choice = 7;
+  const int variant = gemm_variant();
+  if (a.a_ln && !(skinny_ok(a, combo, split_k) && skinny_ln_ok(a))) return DVLA_ERR_UNSUPPORTED;   // only the few-rows kernel normalises
+  // few rows (evaluation-time shapes): one 32 x 32 tile per workgroup, K split over its waves.  Otherwise a row of TILED -- the
+  // cheapest that admits the problem, or the forced one if it does -- or none: the register-staged kernel, the fallback for
+  // shapes the DMA kernels do not take (ragged N, unaligned operands, tiny).
+  const bool few_rows = (variant == DVLA_GEMM_CFG_AUTO || variant == DVLA_GEMM_CFG_FEW_ROWS || a.a_ln) && skinny_ok(a, combo, split_k);
+  int stream_k = 0;               // launch_phase's schedule: 0 plain, 1 hybrid, 2 full
+  const TiledCfg* cfg = few_rows ? nullptr : choose_tiled(a, combo, variant, &stream_k);
+  // k-sums ride on the configurations that carry the summing code, in the fp32-output class (split-K partial sums or fp32 C: the
+  // weight gradients); the other configurations get the column-sum kernel below
+  if (q->ksum_operand != 0 && epi_class(a) == EPI_F32 && cfg && ((cfg->ksum_combos >> combo) & 1)) {
+    a.ksum_op = q->ksum_operand;
+    const int64_t other = q->ksum_operand == 1 ? (q->N + cfg->bn - 1) / cfg->bn : (q->M + cfg->bm - 1) / cfg->bm;
+    a.ksum_parts = KSUM_PARTS * (int)(other < cfg->ksum_share ? other : cfg->ksum_share);
+  }
+  if (few_rows) {
+    launch_skinny(a, stream);
+    g_last_variant = DVLA_GEMM_CFG_FEW_ROWS;
+  } else if (cfg) {
+    cfg->launch(a, combo, split_k, stream, stream_k);   // (a stream-K request falls back to the plain schedule when it does not apply)
+    g_last_variant = a.sk_tiles > 0 ? (stream_k == 1 ? DVLA_GEMM_CFG_PHASE_STREAMK : DVLA_GEMM_CFG_PHASE_STREAMK_FULL) : cfg->id;
 #ifdef DVLA_GEMM_STAMPS
-    else if (variant == 89 && combo == 0 && phase_ok(a, combo)) choice = 89;
+  } else if (variant == DVLA_GEMM_CFG_PHASE_STAMPS && combo == 0 && phase_ok(a, combo)) {      // s_memtime stamps into p.workspace
+    set_tiles<PCfg::BM, PCfg::BN, PCfg::GH>(a);
+    if (epi_class(a) != EPI_P0) return DVLA_ERR_UNSUPPORTED;
+    launch_phase_one<false, false, EPI_P0, PHASE_STAMPS>(a, split_k, stream);
+    g_last_variant = DVLA_GEMM_CFG_PHASE_STAMPS;
 #endif
-    // k-sums ride on the ring kernels and (round 5) on the phase kernel of the fp32-output class (split-K partial sums or fp32 C:
-    // the weight gradients); the other configurations get the column-sum kernel below
-    const bool phase_choice = choice == 5 || choice == 6 || choice == 7;
-    const bool ksum_fused = q->ksum_operand != 0 && epi_class(a) == EPI_F32 &&
-                            (choice == 1 || choice == 3 || choice == 4 || (phase_choice && combo == 3));   // phase: the TT layout (every weight gradient)
-    if (ksum_fused) {
-      a.ksum_op = q->ksum_operand;
-      if (phase_choice) {          // tiles of a tile row (A sums) / tile column (B sums) that share the sum: up to four
-        const int64_t other = q->ksum_operand == 1 ? (q->N + PCfg::BN - 1) / PCfg::BN : (q->M + PCfg::BM - 1) / PCfg::BM;
-        a.ksum_parts = KSUM_PARTS * (int)(other < 4 ? other : 4);
-      }
-    }
-    switch (choice) {
-      case 1: launch_ring<RCfgL>(a, combo, split_k, stream); break;
-      case 3: launch_ring<RCfgS>(a, combo, split_k, stream); break;
-      case 4: launch_ring<RCfgM64>(a, combo, split_k, stream); break;
-      case 5: launch_phase(a, combo, split_k, stream); break;
-      case 6: launch_phase(a, combo, split_k, stream, 1); break;   // falls back to the plain schedule when stream-K does not apply
-      case 7: launch_phase(a, combo, split_k, stream, 2); break;
-      case 11: launch_skinny(a, stream); break;
-#ifdef DVLA_GEMM_STAMPS
-      case 89:      // s_memtime stamps into p.workspace
-        set_tiles<PCfg::BM, PCfg::BN, PCfg::GH>(a);
-        if (epi_class(a) != EPI_P0) return DVLA_ERR_UNSUPPORTED;
-        launch_phase_one<false, false, EPI_P0, PHASE_STAMPS>(a, split_k, stream);
-        break;
-#endif
-      default: launch_cfg<CfgS>(a, combo, split_k, stream); break;
-    }
-    g_last_variant = choice == 11 ? 11 : choice == 1 ? 4 : choice == 3 ? 6 : choice == 4 ? 7 : choice == 5 ? 8
-                   : (choice == 6 || choice == 7) ? (a.sk_tiles > 0 ? (choice == 6 ? 9 : 10) : 8) : choice == 89 ? 89 : 2;
+  } else {
+    launch_reg(a, combo, split_k, stream);
+    g_last_variant = DVLA_GEMM_CFG_REG;
   }
   int rc = dvla_check_launch();
   if (rc != DVLA_OK) return rc;

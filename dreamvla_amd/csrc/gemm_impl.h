@@ -1,14 +1,18 @@
-// gemm.hip -- bf16 MFMA GEMM with fused epilogue for gfx950 (MI355X).
+// gemm_impl.h -- bf16 MFMA GEMM with fused epilogue for gfx950 (MI355X): kernel templates.
 //
 //   C[M,N] = epilogue( A[M,K] . B[N,K]^T ),   fp32 accumulate on v_mfma_f32_32x32x16_bf16
 //
-// Two tile configurations of ONE kernel template (K-tile = 64 in both):
-//   S : 128x128 block tile, 4 waves (2x2), 64x64 per wave (2x2 MFMA tiles),  64 KiB LDS, 2 workgroups / CU   [default]
-//   L : 256x256 block tile, 8 waves (2x4), 128x64 per wave (4x2 MFMA tiles), 128 KiB LDS, 1 workgroup / CU
-// Ablation on MI355X (profiles/r01_gemm_ablation.txt): the S kernel without MFMAs takes 96 % of the full kernel's time
-// and without global loads / LDS writes 58 %, i.e. it is bound by the operand staging path (~22 B/clk/CU from L2), not by
-// the matrix pipe.  The L tile halves that traffic per flop but currently loses more to its single staging set and
-// 1-workgroup occupancy than it gains (805 vs 880 TFLOP/s at 8192^3), so it is opt-in (DVLA_GEMM_VARIANT=3).
+// This file: the REGISTER-STAGED kernel (gemm_kernel, one configuration: CfgS below), the LDS-DMA RING kernels (gemm_ring_kernel,
+// three configurations: RCfg further down, with their own header), the epilogues both share with the phase kernel (gemm_phase.h)
+// and the few-rows kernel (gemm_skinny.h), and the launch helpers.  The host-side choice among them is gemm.hip.
+//
+// The register-staged kernel takes every problem (ragged M / N / K, unaligned operands, any leading dimension) and is the
+// fallback of the DMA kernels: 128x128 block tile, K-tile 64, 4 waves (2x2), 64x64 per wave (2x2 MFMA tiles), 64 KiB LDS,
+// 2 workgroups / CU.  Ablation on MI355X (profiles/r01_gemm_ablation.txt): without MFMAs it takes 96 % of the full kernel's
+// time and without global loads / LDS writes 58 %, i.e. it is bound by the operand staging path (~22 B/clk/CU from L2), not by
+// the matrix pipe.  (A 256x256 configuration of this template with one register set halved that traffic per flop but lost more to
+// its single staging set and 1-workgroup occupancy than it gained -- 805 vs 880 TFLOP/s at 8192^3 -- and is gone; the large tiles
+// are the ring and phase kernels'.)
 //
 // Operands are staged global -> registers -> LDS.  Two register sets per operand: while tile kt is multiplied out of
 // LDS, tile kt+1 waits in one set (written to the other LDS buffer after the MFMAs) and the 16-byte global loads of
@@ -55,17 +59,15 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 
-template <int WM_, int WN_, int TM_, int TN_, bool DEEP_>
-struct Cfg {
-  static constexpr int WM = WM_, WN = WN_, TM = TM_, TN = TN_;
-  static constexpr bool DEEP = DEEP_;   // two register sets (prefetch distance 2) vs one (distance 1: fewer VGPRs)
+// the register-staged configuration: 2 x 2 waves of 2 x 2 MFMA tiles = 128 x 128, 256 threads
+struct CfgS {
+  static constexpr int WM = 2, WN = 2, TM = 2, TN = 2;
   static constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NT = WM * WN * 64;
   static constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2, BUF_BYTES = A_BYTES + B_BYTES;
   static constexpr int SMEM_BYTES = 2 * BUF_BYTES;
   static_assert(NT == 2 * BM && NT == 2 * BN, "staging maps assume 4 x 16 B per thread and operand");
   static_assert(TN == 2, "epilogue patch is 64 columns wide");
 };
-using CfgS = Cfg<2, 2, 2, 2, true>;   // 128 x 128, 256 threads
 
 struct GemmKArgs {
   const bf16_t* A; int64_t lda;
@@ -497,7 +499,7 @@ __global__ __launch_bounds__(CF::NT) void gemm_kernel(GemmKArgs p) {
   const bf16_t* pb[4];
   fast_ptrs<A_T, BM>(pa, p.A, p.lda, m0, p.M, k_begin, t);
   fast_ptrs<B_T, BN>(pb, p.B, p.ldb, n0, p.N, k_begin, t);
-  uint4 ra0[4], rb0[4], ra1[CF::DEEP ? 4 : 1], rb1[CF::DEEP ? 4 : 1];
+  uint4 ra0[4], rb0[4], ra1[4], rb1[4];
   auto load_tile = [&](int kt, uint4 (&ra)[4], uint4 (&rb)[4]) {
     const int64_t k0 = k_begin + (int64_t)kt * BK;
     if (a_fast && kt < nk_full) fast_load<A_T>(ra, pa, p.lda);
@@ -526,76 +528,42 @@ __global__ __launch_bounds__(CF::NT) void gemm_kernel(GemmKArgs p) {
   };
   char* buf0 = smem;
   char* buf1 = smem + CF::BUF_BYTES;
-  if constexpr (CF::DEEP) {
-    if (nk > 0) {
-      load_tile(0, ra0, rb0);
-      store_tile(ra0, rb0, buf0);
-      if (nk > 1) load_tile(1, ra1, rb1);
-    }
-    __syncthreads();
-    int kt = 0;
-    if (a_fast && b_fast) {
-      // steady state, no conditionals inside: the compiler can then count the 8 newer loads and wait with vmcnt(8)
-      // (a conditional prefetch forces s_waitcnt vmcnt(0) at the join and serialises load latency with the MFMAs)
-      while (kt + 3 < nk_full) {
-        fast_load<A_T>(ra0, pa, p.lda); fast_load<B_T>(rb0, pb, p.ldb);
-        __builtin_amdgcn_sched_barrier(0);  // issue the prefetch BEFORE the MFMAs (the scheduler would sink it)
-        compute(buf0);
-        __builtin_amdgcn_sched_barrier(0);  // keep the ds_writes (and their vmcnt wait) BEHIND the MFMAs
-        store_tile(ra1, rb1, buf1);
-        __syncthreads();
-        fast_load<A_T>(ra1, pa, p.lda); fast_load<B_T>(rb1, pb, p.ldb);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(buf1);
-        __builtin_amdgcn_sched_barrier(0);
-        store_tile(ra0, rb0, buf0);
-        __syncthreads();
-        kt += 2;
-      }
-    }
-    for (; kt < nk; kt += 2) {   // remaining (<= 3 full tiles + ragged tail) and the generic / guarded path
-      if (kt + 2 < nk) load_tile(kt + 2, ra0, rb0);
+  if (nk > 0) {
+    load_tile(0, ra0, rb0);
+    store_tile(ra0, rb0, buf0);
+    if (nk > 1) load_tile(1, ra1, rb1);
+  }
+  __syncthreads();
+  int kt = 0;
+  if (a_fast && b_fast) {
+    // steady state, no conditionals inside: the compiler can then count the 8 newer loads and wait with vmcnt(8)
+    // (a conditional prefetch forces s_waitcnt vmcnt(0) at the join and serialises load latency with the MFMAs)
+    while (kt + 3 < nk_full) {
+      fast_load<A_T>(ra0, pa, p.lda); fast_load<B_T>(rb0, pb, p.ldb);
+      __builtin_amdgcn_sched_barrier(0);  // issue the prefetch BEFORE the MFMAs (the scheduler would sink it)
       compute(buf0);
-      if (kt + 1 < nk) store_tile(ra1, rb1, buf1);
+      __builtin_amdgcn_sched_barrier(0);  // keep the ds_writes (and their vmcnt wait) BEHIND the MFMAs
+      store_tile(ra1, rb1, buf1);
       __syncthreads();
-      if (kt + 1 >= nk) break;
-      if (kt + 3 < nk) load_tile(kt + 3, ra1, rb1);
+      fast_load<A_T>(ra1, pa, p.lda); fast_load<B_T>(rb1, pb, p.ldb);
+      __builtin_amdgcn_sched_barrier(0);
       compute(buf1);
-      if (kt + 2 < nk) store_tile(ra0, rb0, buf0);
+      __builtin_amdgcn_sched_barrier(0);
+      store_tile(ra0, rb0, buf0);
       __syncthreads();
+      kt += 2;
     }
-  } else {
-    // one register set: tile kt+1 is loaded while tile kt is multiplied (128 accumulator + 24 fragment registers per
-    // lane leave no room for a second set under the 256-register / 2-waves-per-SIMD budget of a 512-thread workgroup)
-    if (nk > 0) { load_tile(0, ra0, rb0); store_tile(ra0, rb0, buf0); }
+  }
+  for (; kt < nk; kt += 2) {   // remaining (<= 3 full tiles + ragged tail) and the generic / guarded path
+    if (kt + 2 < nk) load_tile(kt + 2, ra0, rb0);
+    compute(buf0);
+    if (kt + 1 < nk) store_tile(ra1, rb1, buf1);
     __syncthreads();
-    int kt = 0;
-    if (a_fast && b_fast) {
-      while (kt + 2 < nk_full) {
-        fast_load<A_T>(ra0, pa, p.lda); fast_load<B_T>(rb0, pb, p.ldb);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(buf0);
-        __builtin_amdgcn_sched_barrier(0);
-        store_tile(ra0, rb0, buf1);
-        __syncthreads();
-        fast_load<A_T>(ra0, pa, p.lda); fast_load<B_T>(rb0, pb, p.ldb);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(buf1);
-        __builtin_amdgcn_sched_barrier(0);
-        store_tile(ra0, rb0, buf0);
-        __syncthreads();
-        kt += 2;
-      }
-    }
-    for (; kt < nk; ++kt) {
-      char* cur = (kt & 1) ? buf1 : buf0;
-      char* nxt = (kt & 1) ? buf0 : buf1;
-      const bool more = kt + 1 < nk;
-      if (more) load_tile(kt + 1, ra0, rb0);
-      compute(cur);
-      if (more) store_tile(ra0, rb0, nxt);
-      __syncthreads();
-    }
+    if (kt + 1 >= nk) break;
+    if (kt + 3 < nk) load_tile(kt + 3, ra1, rb1);
+    compute(buf1);
+    if (kt + 2 < nk) store_tile(ra0, rb0, buf0);
+    __syncthreads();
   }
 
   // (the register-only epilogue of the ring kernels was measured here too: 264 VGPRs -> one workgroup per CU, 30-60 % slower)
@@ -835,8 +803,6 @@ __device__ __forceinline__ void act_bwd8_mul_sel(float (&v)[8], const float (&a)
 // quad_perm + select: 32 VALU, no LDS): afterwards lane 4a + b holds in P[c] piece 2b + g of ROW 4a + c, i.e. instruction c
 // writes rows {4a + c} x all 8 pieces = 8 whole lines.  The same exchange (an involution) turns whole-line LOADS of a
 // store-layout operand (residual, act' operand) into the per-row pieces the accumulator layout needs.
-__device__ __forceinline__ uint32_t dpp_quad_xor1(uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, false); }
-__device__ __forceinline__ uint32_t dpp_quad_xor2(uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xF, 0xF, false); }
 // One exchange stage for two of the four pieces = 8 dwords: O = lane in MASK ? OWN : quad_perm(OTHER), as ONE
 // v_cndmask_b32_dpp per dword.  (The compiler keeps select conditions in arbitrary SGPR pairs, i.e. the VOP3 form of
 // v_cndmask, which has no DPP encoding on gfx9: it emits v_mov_b32_dpp + v_cndmask_b32, twice the VALU slots; the epilogue

@@ -138,8 +138,7 @@ inline bool skinny_ok(const GemmKArgs& a, int combo, int split_k) {
 // on-the-fly LayerNorm of A: the eight-wave variant with every wave's share of K resident in its prefetch registers
 inline bool skinny_ln_ok(const GemmKArgs& a) { return a.K >= 512 && a.K <= (int64_t)16 * 12 * 8 && a.a_ln_eps > 0.f; }
 
-// DVLA_SKINNY_CFG = 0 (default rule) | 1: 4 waves, 12 steps | 2: 8 waves, 12 steps | 3: 8 waves, 6 steps (K <= 768 only) | 4: 8 waves, 20
-// steps (1536 < K <= 3072, at most 512 tiles) -- measurement
+// DVLA_SKINNY_CFG = 0 (default rule) | 1: 4 waves, 12 steps | 2: 8 waves, 12 steps | 3: 8 waves, 6 steps (K <= 768 only) -- measurement
 // (tests/gpu_skinny_perf.py); read per launch
 inline int skinny_cfg() { const char* e = getenv("DVLA_SKINNY_CFG"); return e ? atoi(e) : 0; }
 
@@ -154,13 +153,10 @@ inline void launch_skinny(const GemmKArgs& a, hipStream_t stream) {
     return;
   }
   // long K on few tiles (the DiT head's fc2: K = 3072, 96 tiles): a workgroup alone on its CU is latency-bound -- 14.6 us with
-  // twelve steps in flight and two refills (profiles/r04_skinny_perf.jsonl); twenty of the 24 steps of a wave's share in flight at once (24 would spill)
-  const bool deep = a.K > 16 * 12 * 8 && a.K <= 16 * 24 * 8 && (int64_t)grid.x * grid.y <= 2 * 256;
-  if (cfg == 0) cfg = a.K < 512 ? 1 : (short_k ? 3 : 2);      // (cfg 4 measured: 16.1 us against 14.6 for cfg 2 at K = 3072 -- not the default)
-  if (cfg == 4 && !deep) cfg = 2;
+  // twelve steps in flight and two refills (profiles/r04_skinny_perf.jsonl; twenty steps in flight at once measured 16.1 us: removed)
+  if (cfg == 0) cfg = a.K < 512 ? 1 : (short_k ? 3 : 2);
   if (cfg == 1) hipLaunchKernelGGL((gemm_skinny_kernel<4, false, 12>), grid, dim3(256), 0, stream, a);
   else if (cfg == 3) hipLaunchKernelGGL((gemm_skinny_kernel<8, false, 6>), grid, dim3(512), 0, stream, a);
-  else if (cfg == 4) hipLaunchKernelGGL((gemm_skinny_kernel<8, false, 20>), grid, dim3(512), 0, stream, a);
   else hipLaunchKernelGGL((gemm_skinny_kernel<8, false, 12>), grid, dim3(512), 0, stream, a);
 }
 

@@ -19,10 +19,6 @@ constexpr int LN_THREADS = 256;
 constexpr int LN_MAX_VPL = 4;          // vectors per lane -> cols <= 64*8*4 = 2048
 constexpr int LN_BWD_BLOCKS = 768;     // persistent grid for backward (partial rows)
 
-__device__ __forceinline__ float param_at(const void* p, int f32, int64_t i) {
-  return f32 ? reinterpret_cast<const float*>(p)[i] : bf2f(reinterpret_cast<const bf16_t*>(p)[i]);
-}
-
 __device__ __forceinline__ void unpack8(const uint4& u, float (&f)[8]) {
   f[0] = bf2f((bf16_t)(u.x & 0xffff)); f[1] = bf2f((bf16_t)(u.x >> 16));
   f[2] = bf2f((bf16_t)(u.y & 0xffff)); f[3] = bf2f((bf16_t)(u.y >> 16));

@@ -124,6 +124,18 @@ int dvla_gemm_bf16(const dvla_gemm_params* p, void* stream);
  * kernel (s_memtime stamps into the workspace; only in a library built with DVLA_ABLATIONS=1, tests/probes/gemm_probe.cpp --stamps).
  * Stream-K scratch: 64 MiB + flags per (device, stream), hipMalloc'ed on the first launch that uses it (never while the
  * stream is being captured -- such launches take the plain schedule) and kept; DVLA_GEMM_STREAMK=0 turns the schedule off. */
+enum {                                  /* the numbers above, by name (dvla_set_gemm_variant takes them, dvla_last_gemm_variant reports them) */
+  DVLA_GEMM_CFG_AUTO = 0,
+  DVLA_GEMM_CFG_REG = 2,                /* register-staged 128x128 */
+  DVLA_GEMM_CFG_RING_256 = 4,           /* LDS-DMA ring 256x256 */
+  DVLA_GEMM_CFG_RING_128 = 6,           /* LDS-DMA ring 128x128 */
+  DVLA_GEMM_CFG_RING_256X128 = 7,       /* LDS-DMA ring 256x128, K-tile 64 */
+  DVLA_GEMM_CFG_PHASE = 8,              /* phase kernel, plain schedule */
+  DVLA_GEMM_CFG_PHASE_STREAMK = 9,      /* ... stream-K hybrid schedule */
+  DVLA_GEMM_CFG_PHASE_STREAMK_FULL = 10,/* ... full stream-K schedule */
+  DVLA_GEMM_CFG_FEW_ROWS = 11,
+  DVLA_GEMM_CFG_PHASE_STAMPS = 89       /* timeline build of the phase kernel (DVLA_ABLATIONS=1 libraries only) */
+};
 void dvla_set_gemm_variant(int variant);
 /* 10 = the phase kernel under the FULL stream-K schedule: every tile belongs to the K-iteration ranges, so the groups' tile
  * boundaries (epilogue write bursts) fall at different times for the whole launch instead of in lockstep rounds.

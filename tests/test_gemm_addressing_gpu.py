@@ -1,7 +1,7 @@
 """The GEMM library's ADDRESSING (tests/gpu_checks.py check_gemm_views): every tensor of a dvla_gemm_bf16 call a view into a wider,
 sentinel-filled buffer with its own leading dimension and origin; the periodic residual (res_rows); the fp32 bias; one operand
-at a time misaligned; the stream-K schedules on padded views.  Values against the float64 product of the bf16 operand values
-through the epilogue oracle (TOL_FWD + elem_ulps for bf16 outputs, TOL_F32 for fp32 ones), the buffers around `out` and the
+at a time misaligned; the stream-K schedules on padded views; the cost model's own choice pinned.  Values against the float64
+product of the bf16 operand values through the epilogue oracle (TOL_FWD + elem_ulps for bf16 outputs, TOL_F32 for fp32 ones), the buffers around `out` and the
 pre-activation bit-identical to the sentinel, the same bits as a call on contiguous copies whenever the same configuration ran,
 and the configuration that ran.
 
@@ -12,7 +12,7 @@ and 256), 2 x 2 to 4 x 4 tiles so that tile origins are computed with ld != widt
 N = 96 / 40.  The stream-K schedules at the smallest shape the suite engages them at (20832 x 1024, K = 192).
 
 Measured on an MI355X: 352 cases, all passing, the file runs in about 6 s; the metrics are in
-profiles/r14_parity_gemm_addressing.jsonl ($DVLA_PARITY_REPORT)."""
+profiles/r14_parity_gemm_addressing.jsonl ($DVLA_PARITY_REPORT).  The 13 automatic-choice cases added since run in 5 s together."""
 import pytest
 
 from tests import gpu_checks as G
@@ -112,6 +112,27 @@ for which, mis in (("bias", (0, 9)), ("res", (44, 8)), ("out", (24, 17))):
 for v in (9, 10):
     for rep in range(2):
         case(f"streamk-v{v}-run{rep}", variant=v, expect=v, bias="bf16", residual=True, M=20832, N=1024, K=192)
+
+# ---- the library's own choice (variant 0), pinned: what the cost model of csrc/gemm.hip picked on an MI355X (256 CUs) BEFORE its
+# dispatch became one table -- recorded from that library, so that a table row out of order, a changed constant or a changed tie
+# shows here.  A sweep of that library (M, N in 256 .. 20832 with M x N <= 2^25, K = 64 .. 512, four layouts, plain and
+# bias-tanh-preact: 2350 calls) chose 11, 6, 7, 4 and 8 -- every one of them is below, plain and fused -- and never the stream-K
+# hybrid 9: up to K = 512 its 18 us never pay for the half round it saves (4096 x 4352 x 512, 17 super-tiles, runs 7).  2 is the
+# fallback: a ragged N, a misaligned operand.
+FUSED = EPILOGUES["bias-tanh-preact"]
+case("auto-few-rows-NN-plain", variant=None, expect=11, **LAYOUTS["NN"])
+case("auto-few-rows-NN-fused", variant=None, expect=11, **LAYOUTS["NN"], **FUSED)
+case("auto-ring128-NT-plain", variant=None, expect=6, **LAYOUTS["NT"])                                    # one round: short K
+case("auto-ring128-TT-fused", variant=None, expect=6, **LAYOUTS["TT"], **FUSED)
+case("auto-ring128-three-rounds-NN", variant=None, expect=6, bias="bf16", residual=True, M=20832, N=1024, K=192)
+case("auto-ring256x128-NT-plain", variant=None, expect=7, M=300, N=512, K=256, b_trans=True)               # one round: K >= 256
+case("auto-ring256x128-TN-fused", variant=None, expect=7, M=512, N=320, K=512, a_trans=True, **FUSED)
+case("auto-ring256-NN-plain", variant=None, expect=4, M=2048, N=4352, K=64)                                # 136 tiles of 256^2: one round
+case("auto-ring256-TT-fused", variant=None, expect=4, M=2048, N=4352, K=64, a_trans=True, b_trans=True, **FUSED)
+case("auto-phase-NN-plain", variant=None, expect=8, M=2048, N=4352, K=512)
+case("auto-phase-NT-fused", variant=None, expect=8, M=2048, N=4352, K=512, b_trans=True, **FUSED)
+case("auto-fallback-ragged-N-plain", variant=None, expect=2, M=600, N=328, K=192)
+case("auto-fallback-misaligned-A-fused", variant=None, expect=2, M=600, N=320, K=192, views={"a": (8, 9)}, **FUSED)
 
 
 @pytest.mark.gpu
