@@ -191,6 +191,17 @@ SYMBOLS = {
                                           _P, _P]),
     "dvla_adamw_f32_master_guarded": (C.c_int, [_P, _P, _P, _P, _P, _I64, C.c_double, C.c_double, C.c_double, C.c_double,
                                                 C.c_double, C.c_float, _P, _P]),
+    "dvla_ema_weights": (C.c_int, [C.c_double, _I32, _I64, _I32, C.POINTER(C.c_float)]),
+    "dvla_adamw_bf16_ema": (C.c_int, [_P, _P, _P, _P, _P, _I64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I64, _P,
+                                      C.c_float, C.c_float, _P]),
+    "dvla_adamw_f32_master_ema": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, C.c_double, C.c_double, C.c_double, C.c_double,
+                                            C.c_double, _I64, _P, C.c_float, C.c_float, _P]),
+    "dvla_adamw_bf16_ema_guarded": (C.c_int, [_P, _P, _P, _P, _P, _I64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                              C.c_float, _P, C.POINTER(C.c_float), _I32, _P]),
+    "dvla_adamw_f32_master_ema_guarded": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                    C.c_double, C.c_float, _P, C.POINTER(C.c_float), _I32, _P]),
+    "dvla_ema_swap_f32": (C.c_int, [_P, _P, _P, _I64, _P]),
+    "dvla_ema_swap_bf16": (C.c_int, [_P, _P, _P, _I64, _I32, _P]),
 }
 
 _lib = None

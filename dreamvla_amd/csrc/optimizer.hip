@@ -22,6 +22,11 @@
 //                                   picks the bias-correction scalars of the step count that is then current from a table the
 //                                   host derived (dvla_step_candidates) for every count still possible
 //   dvla_adamw_*_guarded          : the two AdamW kernels reading verdict and scalars from that state; a skipped step moves no byte
+//
+// EMA of the weights (an addition; dvla.h): one more fp32 stream through the step,
+//   dvla_adamw_*_ema(_guarded)    : the four AdamW kernels + e <- lerp(e, p, w) on the parameter just written (ATen's lerp, bit for
+//                                   bit): 30 + 8 = 38 B / parameter on fp32 masters, 14 + 8 = 22 B on bf16; w from dvla_ema_weights
+//   dvla_ema_swap_f32 / _bf16     : the EMA becomes the weights and back (evaluation), the bf16 shadow written in the same pass
 #include "common.h"
 #include "../../include/dvla.h"
 
@@ -306,6 +311,201 @@ __global__ __launch_bounds__(256) void adamw_master_guarded_kernel(MasterArgs a,
   adamw_master_body(a);
 }
 
+// ---- EMA of the weights inside the step (additive; dvla.h) ------------------------------------------------------
+// One more fp32 stream through the loops above: e <- lerp(e, p, w) on the parameter the step has just produced, as ATen's lerp
+// computes it (the expression master_one restates for exp_avg).  The loops are restated, not shared with the kernels above,
+// whose instruction streams are to stay as they are; every element still goes through adam_one / master_one.
+struct EmaArgs { float* e; float w, omw; int w_small; };        // omw = 1 - w in fp32, w_small = |w| < 0.5: lerp's branch
+
+__device__ __forceinline__ EmaArgs ema_args(float* e, float w) {
+  EmaArgs x;
+  x.e = e; x.w = w; x.omw = 1.0f - w; x.w_small = fabsf(w) < 0.5f;
+  return x;
+}
+__device__ __forceinline__ void ema_one(float& e, float p, const EmaArgs& x) {
+  const float d = __fsub_rn(p, e);
+  e = x.w_small ? fmaf(x.w, d, e) : fmaf(-d, x.omw, p);
+}
+
+__device__ __forceinline__ void adamw_master_ema_body(MasterArgs a, EmaArgs x) {
+  float coef = 1.0f;
+  if (a.sumsq) {
+    const float c = a.max_norm / (sqrtf(a.sumsq[0]) + 1e-6f);
+    coef = c < 1.0f ? c : 1.0f;
+  }
+  const int64_t nvec = a.n >> 3;      // 8 elements per thread: 2 x 16 B of each of the five fp32 streams, 16 B of shadow
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
+    float4 p4[2], g4[2], m4[2], v4[2], e4[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      p4[h] = reinterpret_cast<const float4*>(a.p)[2 * i + h]; g4[h] = reinterpret_cast<const float4*>(a.g)[2 * i + h];
+      m4[h] = reinterpret_cast<const float4*>(a.m)[2 * i + h]; v4[h] = reinterpret_cast<const float4*>(a.v)[2 * i + h];
+      e4[h] = reinterpret_cast<const float4*>(x.e)[2 * i + h];
+    }
+    uint32_t sh[4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      master_one(p4[h].x, g4[h].x, m4[h].x, v4[h].x, a, coef);
+      master_one(p4[h].y, g4[h].y, m4[h].y, v4[h].y, a, coef);
+      master_one(p4[h].z, g4[h].z, m4[h].z, v4[h].z, a, coef);
+      master_one(p4[h].w, g4[h].w, m4[h].w, v4[h].w, a, coef);
+      ema_one(e4[h].x, p4[h].x, x); ema_one(e4[h].y, p4[h].y, x); ema_one(e4[h].z, p4[h].z, x); ema_one(e4[h].w, p4[h].w, x);
+      sh[2 * h] = pack2bf(p4[h].x, p4[h].y); sh[2 * h + 1] = pack2bf(p4[h].z, p4[h].w);
+      reinterpret_cast<float4*>(a.p)[2 * i + h] = p4[h];
+      reinterpret_cast<float4*>(a.m)[2 * i + h] = m4[h];
+      reinterpret_cast<float4*>(a.v)[2 * i + h] = v4[h];
+      reinterpret_cast<float4*>(x.e)[2 * i + h] = e4[h];
+    }
+    if (a.sh) reinterpret_cast<uint4*>(a.sh)[i] = make_uint4(sh[0], sh[1], sh[2], sh[3]);
+  }
+  if (blockIdx.x == 0)
+    for (int64_t i = (nvec << 3) + threadIdx.x; i < a.n; i += 256) {
+      float p = a.p[i], m = a.m[i], v = a.v[i], e = x.e[i];
+      master_one(p, a.g[i], m, v, a, coef);
+      ema_one(e, p, x);
+      a.p[i] = p; a.m[i] = m; a.v[i] = v; x.e[i] = e;
+      if (a.sh) a.sh[i] = f2bf(p);
+    }
+}
+
+// The bf16 loop with the EMA (the EMA follows the bf16 value that is written: the parameter as every later reader sees it).
+// adam_one is plain C++, and which of its products the compiler fuses into an fma depends on where the loop stands: inside a
+// function that takes AdamArgs -- shared by the two kernels below -- LLVM's reassociation pass orders the two products of the
+// exp_avg_sq line the other way round than it does in adamw_kernel, the other one is fused, and 2 elements in a million come
+// out one bf16 ulp away.  So the loop is expanded in each kernel body, on the kernel's own argument `a`, where it compiles to
+// adamw_kernel's arithmetic (tests/test_ema_step_gpu.py compares 8 million elements with dvla_adamw_bf16, bit for bit).
+// a: AdamArgs, x: EmaArgs, both kernel-local.  8 elements per thread: 16 B of each bf16 stream, 2 x 16 B of the EMA.
+#define DVLA_ADAMW_EMA_LOOP(a, x)                                                                                              \
+  {                                                                                                                            \
+    float coef = 1.0f;                                                                                                         \
+    if (a.sumsq) {                                                                                                             \
+      const float c = a.max_norm / (sqrtf(a.sumsq[0]) + 1e-6f);                                                                \
+      coef = c < 1.0f ? c : 1.0f;                                                                                              \
+    }                                                                                                                          \
+    const int64_t nvec = a.n >> 3;                                                                                             \
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {                       \
+      const uint4 up = reinterpret_cast<const uint4*>(a.p)[i], ug = reinterpret_cast<const uint4*>(a.g)[i];                    \
+      const uint4 um = reinterpret_cast<const uint4*>(a.m)[i], uv = reinterpret_cast<const uint4*>(a.v)[i];                    \
+      const float4 e0 = reinterpret_cast<const float4*>(x.e)[2 * i], e1 = reinterpret_cast<const float4*>(x.e)[2 * i + 1];     \
+      const uint32_t wp[4] = {up.x, up.y, up.z, up.w}, wg[4] = {ug.x, ug.y, ug.z, ug.w};                                       \
+      const uint32_t wm[4] = {um.x, um.y, um.z, um.w}, wv[4] = {uv.x, uv.y, uv.z, uv.w};                                       \
+      uint32_t op[4], om[4], ov[4];                                                                                            \
+      float e[8] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};                                                           \
+      _Pragma("unroll") for (int k = 0; k < 4; ++k) {                                                                          \
+        float p0 = bf2f((bf16_t)(wp[k] & 0xffff)), p1 = bf2f((bf16_t)(wp[k] >> 16));                                           \
+        float m0 = bf2f((bf16_t)(wm[k] & 0xffff)), m1 = bf2f((bf16_t)(wm[k] >> 16));                                           \
+        float v0 = bf2f((bf16_t)(wv[k] & 0xffff)), v1 = bf2f((bf16_t)(wv[k] >> 16));                                           \
+        adam_one(p0, bf2f((bf16_t)(wg[k] & 0xffff)), m0, v0, a, coef);                                                         \
+        adam_one(p1, bf2f((bf16_t)(wg[k] >> 16)), m1, v1, a, coef);                                                            \
+        op[k] = pack2bf(p0, p1); om[k] = pack2bf(m0, m1); ov[k] = pack2bf(v0, v1);                                             \
+        ema_one(e[2 * k], bf2f((bf16_t)(op[k] & 0xffff)), x);                                                                  \
+        ema_one(e[2 * k + 1], bf2f((bf16_t)(op[k] >> 16)), x);                                                                 \
+      }                                                                                                                        \
+      reinterpret_cast<uint4*>(a.p)[i] = make_uint4(op[0], op[1], op[2], op[3]);                                               \
+      reinterpret_cast<uint4*>(a.m)[i] = make_uint4(om[0], om[1], om[2], om[3]);                                               \
+      reinterpret_cast<uint4*>(a.v)[i] = make_uint4(ov[0], ov[1], ov[2], ov[3]);                                               \
+      reinterpret_cast<float4*>(x.e)[2 * i] = make_float4(e[0], e[1], e[2], e[3]);                                             \
+      reinterpret_cast<float4*>(x.e)[2 * i + 1] = make_float4(e[4], e[5], e[6], e[7]);                                         \
+    }                                                                                                                          \
+    if (blockIdx.x == 0)                                                                                                       \
+      for (int64_t i = (nvec << 3) + threadIdx.x; i < a.n; i += 256) {                                                         \
+        float p = bf2f(a.p[i]), m = bf2f(a.m[i]), v = bf2f(a.v[i]), e = x.e[i];                                                \
+        adam_one(p, bf2f(a.g[i]), m, v, a, coef);                                                                              \
+        const bf16_t pb = f2bf(p);                                                                                             \
+        ema_one(e, bf2f(pb), x);                                                                                               \
+        a.p[i] = pb; a.m[i] = f2bf(m); a.v[i] = f2bf(v); x.e[i] = e;                                                           \
+      }                                                                                                                        \
+  }
+
+__global__ __launch_bounds__(256) void adamw_master_ema_kernel(MasterArgs a, float* ema, float w) {
+  adamw_master_ema_body(a, ema_args(ema, w));
+}
+__global__ __launch_bounds__(256) void adamw_ema_kernel(AdamArgs a, float* ema, float w) {
+  const EmaArgs x = ema_args(ema, w);
+  DVLA_ADAMW_EMA_LOOP(a, x)
+}
+
+// the weights of every step count still possible, by value like VerdictArgs::c; the verdict's row (st->cand) is used
+struct EmaTable { float w[DVLA_STEP_MAX_CANDIDATES]; };
+
+__device__ __forceinline__ float ema_pick(const EmaTable& t, int cand) {
+  float w = t.w[0];
+#pragma unroll
+  for (int k = 1; k < DVLA_STEP_MAX_CANDIDATES; ++k)                 // compare-and-select: t.w[cand] would go through scratch
+    if (cand == k) w = t.w[k];
+  return w;
+}
+
+__global__ __launch_bounds__(256) void adamw_master_ema_guarded_kernel(MasterArgs a, float* ema, EmaTable t,
+                                                                       const dvla_step_state* __restrict__ st) {
+  if (st->ok == 0) return;
+  a.bc2_sqrt = st->bc2_sqrt; a.step_size = st->step_size;
+  adamw_master_ema_body(a, ema_args(ema, ema_pick(t, st->cand)));
+}
+__global__ __launch_bounds__(256) void adamw_ema_guarded_kernel(AdamArgs a, float* ema, EmaTable t,
+                                                                const dvla_step_state* __restrict__ st) {
+  if (st->ok == 0) return;
+  a.inv_bc1 = st->inv_bc1; a.inv_bc2_sqrt = st->inv_bc2_sqrt;
+  const EmaArgs x = ema_args(ema, ema_pick(t, st->cand));
+  DVLA_ADAMW_EMA_LOOP(a, x)
+}
+#undef DVLA_ADAMW_EMA_LOOP
+
+// param <-> ema, and the bf16 shadow of the new param in the same pass (pack2bf / f2bf: the bits of dvla_cast_f32_to_bf16)
+__global__ __launch_bounds__(256) void ema_swap_f32_kernel(float* __restrict__ p, float* __restrict__ e, bf16_t* __restrict__ sh,
+                                                           int64_t n) {
+  const int64_t nvec = n >> 3;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
+    float4 p4[2], e4[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      p4[h] = reinterpret_cast<const float4*>(p)[2 * i + h]; e4[h] = reinterpret_cast<const float4*>(e)[2 * i + h];
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      reinterpret_cast<float4*>(p)[2 * i + h] = e4[h]; reinterpret_cast<float4*>(e)[2 * i + h] = p4[h];
+    }
+    if (sh)
+      reinterpret_cast<uint4*>(sh)[i] = make_uint4(pack2bf(e4[0].x, e4[0].y), pack2bf(e4[0].z, e4[0].w),
+                                                   pack2bf(e4[1].x, e4[1].y), pack2bf(e4[1].z, e4[1].w));
+  }
+  if (blockIdx.x == 0)
+    for (int64_t i = (nvec << 3) + threadIdx.x; i < n; i += 256) {
+      const float a = p[i], b = e[i];
+      p[i] = b; e[i] = a;
+      if (sh) sh[i] = f2bf(b);
+    }
+}
+
+// bf16 parameters cannot hold the fp32 EMA and come back: they are stashed while the rounded EMA stands in for them
+__global__ __launch_bounds__(256) void ema_swap_bf16_kernel(bf16_t* __restrict__ p, const float* __restrict__ e,
+                                                            bf16_t* __restrict__ stash, int64_t n, int restore) {
+  const int64_t nvec = n >> 3;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
+    if (restore) {
+      reinterpret_cast<uint4*>(p)[i] = reinterpret_cast<const uint4*>(stash)[i];
+    } else {
+      const float4 e0 = reinterpret_cast<const float4*>(e)[2 * i], e1 = reinterpret_cast<const float4*>(e)[2 * i + 1];
+      reinterpret_cast<uint4*>(stash)[i] = reinterpret_cast<const uint4*>(p)[i];
+      reinterpret_cast<uint4*>(p)[i] = make_uint4(pack2bf(e0.x, e0.y), pack2bf(e0.z, e0.w), pack2bf(e1.x, e1.y), pack2bf(e1.z, e1.w));
+    }
+  }
+  if (blockIdx.x == 0)
+    for (int64_t i = (nvec << 3) + threadIdx.x; i < n; i += 256) {
+      if (restore) { p[i] = stash[i]; } else { stash[i] = p[i]; p[i] = f2bf(e[i]); }
+    }
+}
+
+inline unsigned step_blocks(int64_t n) {      // 8 elements per thread, at most 4096 blocks (grid-stride beyond)
+  int64_t blocks = (n / 8 + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  if (blocks < 1) blocks = 1;
+  return (unsigned)blocks;
+}
+inline void ema_table(EmaTable& t, const float* w, int n_cand) {
+  for (int j = 0; j < DVLA_STEP_MAX_CANDIDATES; ++j) t.w[j] = w[j < n_cand ? j : n_cand - 1];
+}
+
 }  // namespace
 
 extern "C" int64_t dvla_sumsq_partial_len(void) { return SS_BLOCKS; }
@@ -441,5 +641,119 @@ extern "C" int dvla_adamw_f32_master_guarded(float* param, const float* grad, fl
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(adamw_master_guarded_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a, state);
+  return dvla_check_launch();
+}
+
+// ---- EMA of the weights (additive, ABI 9) -----------------------------------------------------------------------------------
+extern "C" int dvla_ema_weights(double decay, int32_t warmup, int64_t base, int32_t n, float* out) {
+  if (!out || !(decay > 0.0 && decay < 1.0) || base < 1 || n < 0 || n > DVLA_STEP_MAX_CANDIDATES) return DVLA_ERR_ARG;
+  for (int32_t j = 0; j < n; ++j) {
+    const double t = (double)(base + j);      // the 1-based count of applied steps
+    double d = decay;
+    if (warmup) {
+      const double ramp = (1.0 + t) / (10.0 + t);
+      if (ramp < d) d = ramp;
+    }
+    out[j] = (float)(1.0 - d);
+  }
+  return DVLA_OK;
+}
+
+extern "C" int dvla_adamw_bf16_ema(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, float* ema, int64_t n, float lr,
+                                   float beta1, float beta2, float eps, float weight_decay, int64_t step, const float* grad_sumsq,
+                                   float max_norm, float ema_w, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (!param || !grad || !exp_avg || !exp_avg_sq || !ema || n < 0 || step < 1) return DVLA_ERR_ARG;
+  if (n == 0) return DVLA_OK;
+  if (!al16(param) || !al16(grad) || !al16(exp_avg) || !al16(exp_avg_sq) || !al16(ema)) return DVLA_ERR_UNSUPPORTED;
+  AdamArgs a;
+  a.p = reinterpret_cast<bf16_t*>(param); a.g = reinterpret_cast<const bf16_t*>(grad);
+  a.m = reinterpret_cast<bf16_t*>(exp_avg); a.v = reinterpret_cast<bf16_t*>(exp_avg_sq); a.n = n;
+  a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay;
+  bf16_step_scalars(beta1, beta2, step, &a.inv_bc1, &a.inv_bc2_sqrt);
+  a.sumsq = grad_sumsq; a.max_norm = max_norm;
+  hipLaunchKernelGGL(adamw_ema_kernel, dim3(step_blocks(n)), dim3(256), 0, stream, a, ema, ema_w);
+  return dvla_check_launch();
+}
+
+extern "C" int dvla_adamw_f32_master_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
+                                         float* ema, int64_t n, double lr, double beta1, double beta2, double eps,
+                                         double weight_decay, int64_t step, const float* grad_sumsq, float max_norm, float ema_w,
+                                         void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (!param || !grad || !exp_avg || !exp_avg_sq || !ema || n < 0 || step < 1) return DVLA_ERR_ARG;
+  if (n == 0) return DVLA_OK;
+  if (!al16(param) || !al16(grad) || !al16(exp_avg) || !al16(exp_avg_sq) || (shadow_bf16 && !al16(shadow_bf16)) || !al16(ema))
+    return DVLA_ERR_UNSUPPORTED;
+  MasterArgs a;
+  a.p = param; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.sh = reinterpret_cast<bf16_t*>(shadow_bf16); a.n = n;
+  master_fixed_scalars(a, lr, beta1, beta2, eps, weight_decay);
+  master_step_scalars(lr, beta1, beta2, step, &a.bc2_sqrt, &a.step_size);
+  a.sumsq = grad_sumsq; a.max_norm = max_norm;
+  hipLaunchKernelGGL(adamw_master_ema_kernel, dim3(step_blocks(n)), dim3(256), 0, stream, a, ema, ema_w);
+  return dvla_check_launch();
+}
+
+extern "C" int dvla_adamw_bf16_ema_guarded(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, float* ema, int64_t n,
+                                           float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm,
+                                           const dvla_step_state* state, const float* ema_w, int32_t n_cand, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (!param || !grad || !exp_avg || !exp_avg_sq || !ema || !state || !ema_w || n < 0 || n_cand < 1 ||
+      n_cand > DVLA_STEP_MAX_CANDIDATES)
+    return DVLA_ERR_ARG;
+  if (n == 0) return DVLA_OK;
+  if (!al16(param) || !al16(grad) || !al16(exp_avg) || !al16(exp_avg_sq) || !al16(ema) || !al16(state)) return DVLA_ERR_UNSUPPORTED;
+  AdamArgs a;
+  a.p = reinterpret_cast<bf16_t*>(param); a.g = reinterpret_cast<const bf16_t*>(grad);
+  a.m = reinterpret_cast<bf16_t*>(exp_avg); a.v = reinterpret_cast<bf16_t*>(exp_avg_sq); a.n = n;
+  a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay;
+  a.inv_bc1 = a.inv_bc2_sqrt = 0.f;           // the kernel takes both from the state
+  a.sumsq = max_norm > 0.f ? &state->sumsq : nullptr; a.max_norm = max_norm;
+  EmaTable t;
+  ema_table(t, ema_w, n_cand);
+  hipLaunchKernelGGL(adamw_ema_guarded_kernel, dim3(step_blocks(n)), dim3(256), 0, stream, a, ema, t, state);
+  return dvla_check_launch();
+}
+
+extern "C" int dvla_adamw_f32_master_ema_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                                 void* shadow_bf16, float* ema, int64_t n, double lr, double beta1, double beta2,
+                                                 double eps, double weight_decay, float max_norm, const dvla_step_state* state,
+                                                 const float* ema_w, int32_t n_cand, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (!param || !grad || !exp_avg || !exp_avg_sq || !ema || !state || !ema_w || n < 0 || n_cand < 1 ||
+      n_cand > DVLA_STEP_MAX_CANDIDATES)
+    return DVLA_ERR_ARG;
+  if (n == 0) return DVLA_OK;
+  if (!al16(param) || !al16(grad) || !al16(exp_avg) || !al16(exp_avg_sq) || (shadow_bf16 && !al16(shadow_bf16)) || !al16(ema) ||
+      !al16(state))
+    return DVLA_ERR_UNSUPPORTED;
+  MasterArgs a;
+  a.p = param; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.sh = reinterpret_cast<bf16_t*>(shadow_bf16); a.n = n;
+  master_fixed_scalars(a, lr, beta1, beta2, eps, weight_decay);
+  a.bc2_sqrt = a.step_size = 0.f;             // the kernel takes both from the state
+  a.sumsq = max_norm > 0.f ? &state->sumsq : nullptr; a.max_norm = max_norm;
+  EmaTable t;
+  ema_table(t, ema_w, n_cand);
+  hipLaunchKernelGGL(adamw_master_ema_guarded_kernel, dim3(step_blocks(n)), dim3(256), 0, stream, a, ema, t, state);
+  return dvla_check_launch();
+}
+
+extern "C" int dvla_ema_swap_f32(float* param, float* ema, void* shadow_bf16, int64_t n, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (!param || !ema || n < 0) return DVLA_ERR_ARG;
+  if (n == 0) return DVLA_OK;
+  if (!al16(param) || !al16(ema) || (shadow_bf16 && !al16(shadow_bf16))) return DVLA_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(ema_swap_f32_kernel, dim3(step_blocks(n)), dim3(256), 0, stream, param, ema,
+                     reinterpret_cast<bf16_t*>(shadow_bf16), n);
+  return dvla_check_launch();
+}
+
+extern "C" int dvla_ema_swap_bf16(void* param, const float* ema, void* stash, int64_t n, int32_t restore, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (!param || !ema || !stash || n < 0) return DVLA_ERR_ARG;
+  if (n == 0) return DVLA_OK;
+  if (!al16(param) || !al16(ema) || !al16(stash)) return DVLA_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(ema_swap_bf16_kernel, dim3(step_blocks(n)), dim3(256), 0, stream, reinterpret_cast<bf16_t*>(param), ema,
+                     reinterpret_cast<bf16_t*>(stash), n, (int)(restore != 0));
   return dvla_check_launch();
 }

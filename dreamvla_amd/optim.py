@@ -19,8 +19,13 @@ format (indexed in `reducer.params` order), so checkpoints move between this opt
 Guarded step (`skip_nonfinite=True`, an addition): the sums of squares go into one slot per bucket,
 `dvla_step_verdict` adds them, decides on the device whether the step is applied and picks the bias corrections of the step
 count that is then current, and `dvla_adamw_bf16_guarded` / `dvla_adamw_f32_master_guarded` do nothing on a skipped step.
+
+EMA of the weights (`ema_decay=...`, an addition): one fp32 EMA buffer per bucket, updated by the step kernels
+themselves (`dvla_adamw_*_ema`, `dvla_adamw_*_ema_guarded`: e <- lerp(e, p, 1 - decay) on the parameter just written, ATen's
+lerp bit for bit), and exchanged with the weights for evaluation by `dvla_ema_swap_f32` / `dvla_ema_swap_bf16`.
 """
 import collections
+import contextlib
 import ctypes
 import math
 import warnings
@@ -126,14 +131,30 @@ class FlatAdamW(torch.optim.Optimizer):
     talking to the others.  Not covered: a torch LR scheduler (or GradScaler) stepped on the host advances on skipped steps
     too; the guarded step copies 32 bytes back per step and is therefore not graph-capturable; finite gradients whose norm
     overflows fp32 are skipped as well.  With the guard on, `step_count` is the applied count last confirmed by the device
-    (it lags by up to WINDOW steps; `applied_steps` is exact)."""
+    (it lags by up to WINDOW steps; `applied_steps` is exact).
 
-    WINDOW = 8      # guarded steps in flight before step() waits for the oldest readback
+    ema_decay=d, 0 < d < 1 (None by default: no buffer, and the launches above): every bucket also carries an fp32 EMA of
+    its parameters (fp32 for bf16 buckets too: 1 - d is below a bf16 ulp), initialised from them here and updated inside the
+    step kernel, e <- lerp(e, p, 1 - d(t)) on the stored parameter, bit for bit what `ema.lerp_(p.float(), 1 - d(t))` gives;
+    parameters, moments and shadows are those of the step without it.  ema_warmup=True: d(t) = min(d, (1 + t) / (10 + t)),
+    t the 1-based count of applied steps (a skipped step neither moves the EMA nor advances t).  Parameters that receive no
+    gradient keep their initial copy.  `ema_weights()` is the context in which the model computes on the EMA;
+    `ema_model_state_dict(model)` the state dict an evaluation script loads; `ema_state_dict()` / `load_ema_state_dict()`
+    the checkpoint (state_dict() / load_state_dict() keep their formats and do not touch the EMA); `ema_reset()` restarts
+    it from the current parameters.  Under data parallelism every rank steps the same reduced buckets, so every rank holds
+    the same EMA without communication."""
+
+    WINDOW = 8     # guarded steps in flight before step() waits for the oldest readback
 
     def __init__(self, reducer, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, amsgrad=False,
-                 maximize=False, skip_nonfinite=False):
+                 maximize=False, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
         if amsgrad or maximize:
             raise ValueError("FlatAdamW: amsgrad and maximize are not supported")
+        if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
+            raise ValueError(f"FlatAdamW: ema_decay must lie strictly between 0 and 1 ({ema_decay!r} given)")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self._ema_active = False            # inside ema_weights()
         self.skip_nonfinite = bool(skip_nonfinite)
         if self.skip_nonfinite and len(reducer.buckets) > _lib.STEP_MAX_BUCKETS:
             raise ValueError(f"FlatAdamW(skip_nonfinite=True): at most {_lib.STEP_MAX_BUCKETS} gradient buckets "
@@ -158,7 +179,11 @@ class FlatAdamW(torch.optim.Optimizer):
             if g.dtype == torch.float32:                        # fp32 masters: + the flat bf16 shadow (same offsets)
                 ent["sh"] = torch.zeros(g.numel(), dtype=torch.bfloat16, device=g.device)
                 ops.register_flat_shadow(flat_p, ent["sh"])
+            if self.ema_decay is not None:                      # always fp32, at the same offsets
+                ent["ema"] = flat_p.to(torch.float32, copy=True)
             self.flat.append(ent)
+        if self.ema_decay is not None:
+            self._ema_w = (ctypes.c_float * _lib.STEP_MAX_CANDIDATES)()       # dvla_ema_weights writes it, the step reads it
         self.master_mode = any("sh" in s for s in self.flat)
         dev = reducer.buckets[0]["flat"].device
         self._sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -221,9 +246,26 @@ class FlatAdamW(torch.optim.Optimizer):
         state = self._state.data_ptr()
         check(lib.dvla_step_verdict(self._slots.data_ptr(), len(self.flat), self._sumsq.data_ptr(), state, confirmed, n_cand,
                                     self._cand, stream), "dvla_step_verdict")
+        ema = self.ema_decay is not None
+        if ema:     # the weights of the same candidate counts confirmed + 1 + j; the kernels pick the verdict's row
+            check(lib.dvla_ema_weights(self.ema_decay, int(self.ema_warmup), confirmed + 1, n_cand, self._ema_w), "dvla_ema_weights")
         for bi, s in enumerate(self.flat):
             for (lo, hi) in self._ranges(bi):
                 if hi <= lo:
+                    continue
+                if ema and "sh" in s:
+                    o = 4 * lo
+                    check(lib.dvla_adamw_f32_master_ema_guarded(
+                        s["p"].data_ptr() + o, s["g"].data_ptr() + o, s["m"].data_ptr() + o, s["v"].data_ptr() + o,
+                        s["sh"].data_ptr() + 2 * lo, s["ema"].data_ptr() + o, hi - lo, lr, float(b1), float(b2), eps, wd, max_norm,
+                        state, self._ema_w, n_cand, stream), "dvla_adamw_f32_master_ema_guarded")
+                    continue
+                if ema:
+                    o = 2 * lo
+                    check(lib.dvla_adamw_bf16_ema_guarded(
+                        s["p"].data_ptr() + o, s["g"].data_ptr() + o, s["m"].data_ptr() + o, s["v"].data_ptr() + o,
+                        s["ema"].data_ptr() + 4 * lo, hi - lo, lr, float(b1), float(b2), eps, wd, max_norm, state, self._ema_w,
+                        n_cand, stream), "dvla_adamw_bf16_ema_guarded")
                     continue
                 if "sh" in s:
                     o = 4 * lo
@@ -310,11 +352,16 @@ class FlatAdamW(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
+        if self._ema_active:
+            raise RuntimeError("FlatAdamW.step() inside ema_weights(): the model holds the EMA weights, not the training weights")
         if self.skip_nonfinite:
             return self._guarded_step()
         lib = _lib.load()
         stream = torch.cuda.current_stream().cuda_stream
         self.step_count += 1
+        ema = self.ema_decay is not None
+        if ema:
+            check(lib.dvla_ema_weights(self.ema_decay, int(self.ema_warmup), self.step_count, 1, self._ema_w), "dvla_ema_weights")
         grp = self.param_groups[0]
         lr, (b1, b2), eps, wd = float(grp["lr"]), grp["betas"], float(grp["eps"]), float(grp["weight_decay"])
         clip = self.max_grad_norm is not None
@@ -326,6 +373,22 @@ class FlatAdamW(torch.optim.Optimizer):
         for bi, s in enumerate(self.flat):
             for (lo, hi) in self._ranges(bi):
                 if hi <= lo:
+                    continue
+                if ema and "sh" in s:
+                    o = 4 * lo
+                    check(lib.dvla_adamw_f32_master_ema(
+                        s["p"].data_ptr() + o, s["g"].data_ptr() + o, s["m"].data_ptr() + o, s["v"].data_ptr() + o,
+                        s["sh"].data_ptr() + 2 * lo, s["ema"].data_ptr() + o, hi - lo, lr, float(b1), float(b2), eps, wd,
+                        self.step_count, self._sumsq.data_ptr() if clip else None, self.max_grad_norm if clip else 0.0,
+                        self._ema_w[0], stream), "dvla_adamw_f32_master_ema")
+                    continue
+                if ema:
+                    o = 2 * lo
+                    check(lib.dvla_adamw_bf16_ema(
+                        s["p"].data_ptr() + o, s["g"].data_ptr() + o, s["m"].data_ptr() + o, s["v"].data_ptr() + o,
+                        s["ema"].data_ptr() + 4 * lo, hi - lo, lr, float(b1), float(b2), eps, wd, self.step_count,
+                        self._sumsq.data_ptr() if clip else None, self.max_grad_norm if clip else 0.0, self._ema_w[0], stream),
+                        "dvla_adamw_bf16_ema")
                     continue
                 if "sh" in s:
                     o = 4 * lo      # fp32 byte offset
@@ -380,6 +443,101 @@ class FlatAdamW(torch.optim.Optimizer):
 
     def _layout(self):
         return flat_layout(self.reducer)
+
+    # ---- EMA of the weights (ema_decay=...) ------------------------------------------------------------------------------------
+    def _require_ema(self, what):
+        if self.ema_decay is None:
+            raise RuntimeError(f"FlatAdamW.{what}: construct the optimizer with ema_decay=...")
+        if self._ema_active:
+            raise RuntimeError(f"FlatAdamW.{what} inside ema_weights(): the EMA buffers are swapped with the training weights")
+
+    def ema_reset(self):
+        """the EMA restarts from the current parameters (after a checkpoint was loaded into the model, say)"""
+        self._require_ema("ema_reset()")
+        for s in self.flat:
+            s["ema"].copy_(s["p"])
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the EMA values are the model's weights; on exit the training weights are back bit for bit, also
+        when the body raises.  fp32 masters: one launch per bucket exchanges the master and the EMA buffer in place and writes
+        the bf16 shadow of what the master buffer then holds, so no cast and no ops.invalidate_shadows() is needed; bf16 buckets
+        are stashed (allocated on entry, freed on exit) and hold the EMA rounded to bf16.  Works before the first step and right
+        after load_state_dict.  step(), nesting and the other ema_* methods raise RuntimeError inside.  A RolloutEngine built
+        outside the context must be reset() or rebuilt inside it (and again after it): its captured graphs read the same
+        addresses, but its per-instruction and per-frame caches were computed from the other weights."""
+        self._require_ema("ema_weights()")
+        lib = _lib.load()
+        self._ema_active = True
+        stashes = {}
+        try:
+            self._ema_swap(lib, stashes, restore=0)
+            yield self
+        finally:
+            self._ema_swap(lib, stashes, restore=1)
+            self._ema_active = False
+
+    def _ema_swap(self, lib, stashes, restore):
+        """whole buckets, on the current stream.  restore: undo exactly what the entry did (a bucket the entry did not reach --
+        it raised -- is left alone)"""
+        stream = torch.cuda.current_stream().cuda_stream
+        for bi, s in enumerate(self.flat):
+            n = s["p"].numel()
+            if restore and bi not in stashes:
+                continue
+            if "sh" in s:
+                check(lib.dvla_ema_swap_f32(s["p"].data_ptr(), s["ema"].data_ptr(), s["sh"].data_ptr(), n, stream),
+                      "dvla_ema_swap_f32")
+                b = self.reducer.buckets[bi]
+                for p, off in zip(b["params"], b["offsets"]):      # the shadow was written in that launch
+                    ops.adopt_shadow(p, s["sh"][off:off + p.numel()].view(p.shape))
+                stashes[bi] = None
+                continue
+            stash = stashes[bi] if restore else torch.empty_like(s["p"])
+            check(lib.dvla_ema_swap_bf16(s["p"].data_ptr(), s["ema"].data_ptr(), stash.data_ptr(), n, restore, stream),
+                  "dvla_ema_swap_bf16")
+            stashes[bi] = stash
+        if restore:
+            stashes.clear()
+
+    def ema_state_dict(self):
+        """{"decay", "warmup", "ema": {i: fp32 clone in the shape of reducer.params[i]}}"""
+        self._require_ema("ema_state_dict()")
+        out = {}
+        for lay, s in zip(self._layout(), self.flat):
+            for i, off, shape in lay:
+                out[i] = s["ema"][off:off + math.prod(shape)].view(shape).clone()
+        return {"decay": self.ema_decay, "warmup": self.ema_warmup, "ema": dict(sorted(out.items()))}
+
+    def load_ema_state_dict(self, sd):
+        """the inverse of ema_state_dict(); a tensor of another shape than its parameter raises ValueError"""
+        self._require_ema("load_ema_state_dict()")
+        ema = sd["ema"]
+        layout = self._layout()
+        for lay in layout:
+            for i, off, shape in lay:
+                if i not in ema or tuple(ema[i].shape) != tuple(shape):
+                    got = tuple(ema[i].shape) if i in ema else None
+                    raise ValueError(f"FlatAdamW.load_ema_state_dict: parameter {i} has shape {tuple(shape)}, the checkpoint's "
+                                     f"EMA {got}")
+        for lay, s in zip(layout, self.flat):
+            for i, off, shape in lay:
+                s["ema"][off:off + math.prod(shape)].copy_(ema[i].reshape(-1))
+        self.ema_decay, self.ema_warmup = float(sd["decay"]), bool(sd["warmup"])
+
+    def ema_model_state_dict(self, model):
+        """model.state_dict() with every entry that belongs to a parameter of reducer.params (matched by identity through
+        named_parameters) replaced by its EMA value in the entry's dtype: what an evaluation script loads"""
+        self._require_ema("ema_model_state_dict()")
+        where = {}
+        for lay, s in zip(self._layout(), self.flat):
+            for i, off, shape in lay:
+                where[id(self.reducer.params[i])] = s["ema"][off:off + math.prod(shape)].view(shape)
+        sd = model.state_dict()
+        for name, p in model.named_parameters(remove_duplicate=False):
+            if id(p) in where and name in sd:
+                sd[name] = where[id(p)].to(sd[name].dtype, copy=True)
+        return sd
 
     def state_dict(self):
         """master mode: torch.optim.AdamW's format (see torch_state_from_flat).  bf16 buckets only: step count, hyper-parameters

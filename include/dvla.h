@@ -432,6 +432,42 @@ int dvla_adamw_bf16_guarded(void* param, const void* grad, void* exp_avg, void* 
 int dvla_adamw_f32_master_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
                                   int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay,
                                   float max_norm, const dvla_step_state* state, void* stream);
+/* (additive, ABI 9) EMA of the weights inside the step.  The EMA buffer is fp32 whatever the parameter dtype
+ * (a bf16 EMA with 1 - decay below a bf16 ulp would never move), at the parameter's offsets.  After an element's AdamW update
+ * has produced the STORED parameter p (the fp32 master; the bf16 value that is written, widened), e <- lerp(e, p, w) as ATen
+ * computes it: diff = p - e (rounded), then fma(w, diff, e) if |w| < 0.5 else fma(-diff, 1 - w, p).  Parameters, moments and
+ * shadows come out bit-identical to the step without `ema`: the AdamW part is the twin's element function on the same scalars.
+ * dvla_ema_weights: no launch; the one place the weight is derived.  out[j], j < n, = (float)(1 - d(base + j)) formed in
+ *   double, where t = base + j is the 1-based count of applied steps and d(t) = decay, or with warmup != 0
+ *   d(t) = min(decay, (1 + t) / (10 + t)) (the timm / diffusers warm-up).  0 < decay < 1, base >= 1,
+ *   0 <= n <= DVLA_STEP_MAX_CANDIDATES, out not NULL: DVLA_ERR_ARG otherwise.
+ * dvla_adamw_bf16_ema / dvla_adamw_f32_master_ema: dvla_adamw_bf16 / dvla_adamw_f32_master + `ema` (n floats, 16-byte
+ *   aligned, not NULL) and its weight `ema_w` (dvla_ema_weights of `step`).
+ * dvla_adamw_bf16_ema_guarded / dvla_adamw_f32_master_ema_guarded: the guarded twins + `ema` and `ema_w`, a HOST table of
+ *   n_cand weights (dvla_ema_weights(decay, warmup, base, n_cand) for the `base` and n_cand given to dvla_step_candidates /
+ *   dvla_step_verdict), copied into the kernel arguments; row state->cand is used.  state->ok == 0: nothing is read or
+ *   written, the EMA included, so a skipped step neither moves the EMA nor advances its warm-up.
+ * dvla_ema_swap_f32: param[i] <-> ema[i] for i < n, and, if shadow_bf16 != NULL, shadow[i] = the RNE bf16 of the new param[i]
+ *   (dvla_cast_f32_to_bf16's bits).  Twice in a row restores everything.
+ * dvla_ema_swap_bf16: restore == 0: stash[i] = param[i], then param[i] = the RNE bf16 of ema[i]; restore != 0:
+ *   param[i] = stash[i].  The EMA is only read.
+ * Every pointer 16-byte aligned (DVLA_ERR_UNSUPPORTED otherwise); n == 0: DVLA_OK, nothing launched. */
+int dvla_ema_weights(double decay, int32_t warmup, int64_t base, int32_t n, float* out);
+int dvla_adamw_bf16_ema(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, float* ema, int64_t n, float lr,
+                        float beta1, float beta2, float eps, float weight_decay, int64_t step, const float* grad_sumsq,
+                        float max_norm, float ema_w, void* stream);
+int dvla_adamw_f32_master_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, float* ema,
+                              int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                              const float* grad_sumsq, float max_norm, float ema_w, void* stream);
+int dvla_adamw_bf16_ema_guarded(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, float* ema, int64_t n, float lr,
+                                float beta1, float beta2, float eps, float weight_decay, float max_norm,
+                                const dvla_step_state* state, const float* ema_w, int32_t n_cand, void* stream);
+int dvla_adamw_f32_master_ema_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
+                                      float* ema, int64_t n, double lr, double beta1, double beta2, double eps,
+                                      double weight_decay, float max_norm, const dvla_step_state* state, const float* ema_w,
+                                      int32_t n_cand, void* stream);
+int dvla_ema_swap_f32(float* param, float* ema, void* shadow_bf16, int64_t n, void* stream);
+int dvla_ema_swap_bf16(void* param, const float* ema, void* stash, int64_t n, int32_t restore, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Token assembly (models/dreamvla_model.py:739-759): out[b, s, t, :] = part_k[b, s, t - tok_begin_k, :] + pos[s, :]
