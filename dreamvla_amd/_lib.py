@@ -113,6 +113,12 @@ class StepState(C.Structure):
 
 
 STEP_READBACK_BYTES = 32
+STEP_MAX_GROUPS = 64                                 # DVLA_STEP_MAX_GROUPS
+
+
+class GroupRow(C.Structure):
+    """dvla_group_row: what dvla_group_scalars derives for one parameter group"""
+    _fields_ = [("decay", C.c_float), ("lr", C.c_float), ("weight_decay", C.c_float), ("step_size", C.c_float * STEP_MAX_CANDIDATES)]
 
 
 # every symbol include/dvla.h declares: (name, restype, argtypes)
@@ -202,6 +208,13 @@ SYMBOLS = {
                                                     C.c_double, C.c_float, _P, C.POINTER(C.c_float), _I32, _P]),
     "dvla_ema_swap_f32": (C.c_int, [_P, _P, _P, _I64, _P]),
     "dvla_ema_swap_bf16": (C.c_int, [_P, _P, _P, _I64, _I32, _P]),
+    "dvla_group_scalars": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), _I32, C.c_double, C.c_double, _I64, _I32,
+                                     C.POINTER(GroupRow)]),
+    "dvla_adamw_bf16_grouped": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P, _I32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                          C.c_float, C.c_float, C.c_float, _I64, _P, C.c_float, _P, C.POINTER(C.c_float), _I32, _P]),
+    "dvla_adamw_f32_master_grouped": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _P, _I32, C.POINTER(C.c_double),
+                                                C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, _I64, _P, C.c_float, _P,
+                                                C.POINTER(C.c_float), _I32, _P]),
 }
 
 _lib = None

@@ -209,8 +209,9 @@ inline void bf16_step_scalars(float beta1, float beta2, int64_t step, float* inv
   const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
   *inv_bc1 = (float)(1.0 / bc1); *inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
 }
+inline float master_decay(double lr, double weight_decay) { return (float)(1.0 - lr * weight_decay); }
 inline void master_fixed_scalars(MasterArgs& a, double lr, double beta1, double beta2, double eps, double weight_decay) {
-  a.decay = (float)(1.0 - lr * weight_decay);
+  a.decay = master_decay(lr, weight_decay);
   a.w1 = (float)(1.0 - beta1);
   a.w1_small = fabsf(a.w1) < 0.5f;
   a.beta2 = (float)beta2;
@@ -496,6 +497,199 @@ __global__ __launch_bounds__(256) void ema_swap_bf16_kernel(bf16_t* __restrict__
     }
 }
 
+// ---- parameter groups: per-group lr and weight decay in one launch per bucket (additive; dvla.h) ----------------
+// A group map gives every vector of 8 elements its group (one byte; 255, or any id >= n_groups: the vector is left alone, nothing
+// of it read or written).  What depends on the group travels by value in the kernel arguments, as VerdictArgs::c does; wave 0
+// puts one row per group into LDS (constant indices only: a lane-varying index into a by-value array goes through scratch; the
+// candidate row is wave-uniform and picked by compare-and-select), and every vector looks its row up by its map byte.  The
+// map byte of the next round is fetched before this round's streams, so the dependent load is off the critical path.
+template <int NC>
+struct GroupTab {                   // master: x = decay, y = step_size per candidate count.  bf16: x = lr, y[0] = wd (NC = 1)
+  float x[DVLA_STEP_MAX_GROUPS];
+  float y[NC][DVLA_STEP_MAX_GROUPS];
+};
+
+template <int NC>
+__device__ __forceinline__ float2 group_row(const GroupTab<NC>& t, int n_groups, int cand) {      // the row of group threadIdx.x
+  float x = 0.f, y = 0.f;
+#pragma unroll
+  for (int g = 0; g < DVLA_STEP_MAX_GROUPS; ++g) {
+    if (g >= n_groups) break;                                        // uniform: two or three groups cost two or three rounds
+    float yg = t.y[0][g];
+#pragma unroll
+    for (int k = 1; k < NC; ++k)
+      if (cand == k) yg = t.y[k][g];
+    if ((int)threadIdx.x == g) { x = t.x[g]; y = yg; }
+  }
+  return make_float2(x, y);
+}
+
+__device__ __forceinline__ float clip_coef(const float* sumsq, float max_norm) {
+  if (!sumsq) return 1.0f;
+  const float c = max_norm / (sqrtf(sumsq[0]) + 1e-6f);
+  return c < 1.0f ? c : 1.0f;
+}
+
+// GUARD: the verdict and the step-dependent scalars come from *st (adamw_master_guarded_kernel); EMA: + ema_one on the
+// parameter just written (adamw_master_ema_body).  Every element goes through master_one, on a copy of the arguments that
+// carries its group's decay and step_size.
+template <bool GUARD, bool EMA>
+__global__ __launch_bounds__(256) void adamw_master_grouped_kernel(MasterArgs a, const uint8_t* __restrict__ map, int n_groups,
+                                                                   GroupTab<GUARD ? DVLA_STEP_MAX_CANDIDATES : 1> t, float* ema,
+                                                                   EmaTable wt, const dvla_step_state* __restrict__ st) {
+  __shared__ float2 rows[DVLA_STEP_MAX_GROUPS];
+  int cand = 0;
+  if (GUARD) {
+    if (st->ok == 0) return;
+    a.bc2_sqrt = st->bc2_sqrt;
+    cand = st->cand;
+  }
+  if (threadIdx.x < DVLA_STEP_MAX_GROUPS) rows[threadIdx.x] = group_row(t, n_groups, cand);
+  __syncthreads();
+  const EmaArgs x = ema_args(ema, EMA ? ema_pick(wt, cand) : 0.f);
+  const float coef = clip_coef(a.sumsq, a.max_norm);
+  const int64_t nvec = a.n >> 3, stride = (int64_t)gridDim.x * 256;
+  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  unsigned id = i < nvec ? map[i] : 255u;
+  while (i < nvec) {
+    const int64_t nx = i + stride;
+    const unsigned id_nx = nx < nvec ? map[nx] : 255u;
+    if (id < (unsigned)n_groups) {
+      const float2 r = rows[id];
+      MasterArgs b = a;
+      b.decay = r.x; b.step_size = r.y;
+      float4 p4[2], g4[2], m4[2], v4[2], e4[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        p4[h] = reinterpret_cast<const float4*>(a.p)[2 * i + h]; g4[h] = reinterpret_cast<const float4*>(a.g)[2 * i + h];
+        m4[h] = reinterpret_cast<const float4*>(a.m)[2 * i + h]; v4[h] = reinterpret_cast<const float4*>(a.v)[2 * i + h];
+        if (EMA) e4[h] = reinterpret_cast<const float4*>(x.e)[2 * i + h];
+      }
+      uint32_t sh[4];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        master_one(p4[h].x, g4[h].x, m4[h].x, v4[h].x, b, coef);
+        master_one(p4[h].y, g4[h].y, m4[h].y, v4[h].y, b, coef);
+        master_one(p4[h].z, g4[h].z, m4[h].z, v4[h].z, b, coef);
+        master_one(p4[h].w, g4[h].w, m4[h].w, v4[h].w, b, coef);
+        sh[2 * h] = pack2bf(p4[h].x, p4[h].y); sh[2 * h + 1] = pack2bf(p4[h].z, p4[h].w);
+        reinterpret_cast<float4*>(a.p)[2 * i + h] = p4[h];
+        reinterpret_cast<float4*>(a.m)[2 * i + h] = m4[h];
+        reinterpret_cast<float4*>(a.v)[2 * i + h] = v4[h];
+        if (EMA) {
+          ema_one(e4[h].x, p4[h].x, x); ema_one(e4[h].y, p4[h].y, x); ema_one(e4[h].z, p4[h].z, x); ema_one(e4[h].w, p4[h].w, x);
+          reinterpret_cast<float4*>(x.e)[2 * i + h] = e4[h];
+        }
+      }
+      if (a.sh) reinterpret_cast<uint4*>(a.sh)[i] = make_uint4(sh[0], sh[1], sh[2], sh[3]);
+    }
+    i = nx; id = id_nx;
+  }
+  if (blockIdx.x == 0 && (nvec << 3) < a.n) {      // the ragged tail (n % 8 elements) belongs to the last map byte
+    const unsigned idt = map[nvec];
+    if (idt < (unsigned)n_groups) {
+      const float2 r = rows[idt];
+      MasterArgs b = a;
+      b.decay = r.x; b.step_size = r.y;
+      for (int64_t j = (nvec << 3) + threadIdx.x; j < a.n; j += 256) {
+        float p = a.p[j], m = a.m[j], v = a.v[j];
+        master_one(p, a.g[j], m, v, b, coef);
+        a.p[j] = p; a.m[j] = m; a.v[j] = v;
+        if (EMA) { float e = x.e[j]; ema_one(e, p, x); x.e[j] = e; }
+        if (a.sh) a.sh[j] = f2bf(p);
+      }
+    }
+  }
+}
+
+// The bf16 element function with its roundings written out.  adam_one is plain C++ and the compiler decides which of its
+// products to fuse, differently in adamw_kernel's vector loop and in its ragged-tail loop; with lr and wd per vector instead of
+// per launch it would decide once more.  So both forms are restated here as adamw_kernel's instructions have them (nothing is
+// contracted inside these two functions; tests/test_param_groups_gpu.py compares 9 million elements with dvla_adamw_bf16):
+//   vector loop: decay = fma(-lr, wd, 1), v = fma(beta2, v, ((1 - beta2) g) g), p = fma(decay, p, -((lr inv_bc1) (m / denom)))
+//   tail loop:   decay = 1 - lr wd,       v = beta2 v + ((1 - beta2) g) g,     p = decay p - (lr inv_bc1) (m / denom)
+// and in both m = fma(1 - beta1, g - m, m), denom = fma(sqrt(v), inv_bc2_sqrt, eps).
+template <bool TAIL>
+__device__ __forceinline__ void adam_group_one(float& p, float g, float& m, float& v, const AdamArgs& a, float lr, float wd,
+                                               float coef) {
+#pragma clang fp contract(off)
+  g = bf2f(f2bf(g * coef));
+  const float gg = ((1.0f - a.beta2) * g) * g, step = lr * a.inv_bc1;
+  v = TAIL ? a.beta2 * v + gg : fmaf(a.beta2, v, gg);
+  m = fmaf(1.0f - a.beta1, g - m, m);
+  const float q = step * (m / fmaf(sqrtf(v), a.inv_bc2_sqrt, a.eps));
+  p = TAIL ? (1.0f - lr * wd) * p - q : fmaf(fmaf(-lr, wd, 1.0f), p, -q);
+}
+
+template <bool GUARD, bool EMA>
+__global__ __launch_bounds__(256) void adamw_grouped_kernel(AdamArgs a, const uint8_t* __restrict__ map, int n_groups, GroupTab<1> t,
+                                                            float* ema, EmaTable wt, const dvla_step_state* __restrict__ st) {
+  __shared__ float2 rows[DVLA_STEP_MAX_GROUPS];
+  int cand = 0;
+  if (GUARD) {
+    if (st->ok == 0) return;
+    a.inv_bc1 = st->inv_bc1; a.inv_bc2_sqrt = st->inv_bc2_sqrt;
+    cand = st->cand;
+  }
+  if (threadIdx.x < DVLA_STEP_MAX_GROUPS) rows[threadIdx.x] = group_row(t, n_groups, 0);
+  __syncthreads();
+  const EmaArgs x = ema_args(ema, EMA ? ema_pick(wt, cand) : 0.f);
+  const float coef = clip_coef(a.sumsq, a.max_norm);
+  const int64_t nvec = a.n >> 3, stride = (int64_t)gridDim.x * 256;
+  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  unsigned id = i < nvec ? map[i] : 255u;
+  while (i < nvec) {
+    const int64_t nx = i + stride;
+    const unsigned id_nx = nx < nvec ? map[nx] : 255u;
+    if (id < (unsigned)n_groups) {
+      const float2 r = rows[id];      // lr, wd
+      const uint4 up = reinterpret_cast<const uint4*>(a.p)[i], ug = reinterpret_cast<const uint4*>(a.g)[i];
+      const uint4 um = reinterpret_cast<const uint4*>(a.m)[i], uv = reinterpret_cast<const uint4*>(a.v)[i];
+      float4 e0, e1;
+      if (EMA) { e0 = reinterpret_cast<const float4*>(x.e)[2 * i]; e1 = reinterpret_cast<const float4*>(x.e)[2 * i + 1]; }
+      const uint32_t wp[4] = {up.x, up.y, up.z, up.w}, wg[4] = {ug.x, ug.y, ug.z, ug.w};
+      const uint32_t wm[4] = {um.x, um.y, um.z, um.w}, wv[4] = {uv.x, uv.y, uv.z, uv.w};
+      uint32_t op[4], om[4], ov[4];
+      float e[8];
+      if (EMA) { e[0] = e0.x; e[1] = e0.y; e[2] = e0.z; e[3] = e0.w; e[4] = e1.x; e[5] = e1.y; e[6] = e1.z; e[7] = e1.w; }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float p0 = bf2f((bf16_t)(wp[k] & 0xffff)), p1 = bf2f((bf16_t)(wp[k] >> 16));
+        float m0 = bf2f((bf16_t)(wm[k] & 0xffff)), m1 = bf2f((bf16_t)(wm[k] >> 16));
+        float v0 = bf2f((bf16_t)(wv[k] & 0xffff)), v1 = bf2f((bf16_t)(wv[k] >> 16));
+        adam_group_one<false>(p0, bf2f((bf16_t)(wg[k] & 0xffff)), m0, v0, a, r.x, r.y, coef);
+        adam_group_one<false>(p1, bf2f((bf16_t)(wg[k] >> 16)), m1, v1, a, r.x, r.y, coef);
+        op[k] = pack2bf(p0, p1); om[k] = pack2bf(m0, m1); ov[k] = pack2bf(v0, v1);
+        if (EMA) {      // the EMA follows the bf16 value that is written
+          ema_one(e[2 * k], bf2f((bf16_t)(op[k] & 0xffff)), x);
+          ema_one(e[2 * k + 1], bf2f((bf16_t)(op[k] >> 16)), x);
+        }
+      }
+      reinterpret_cast<uint4*>(a.p)[i] = make_uint4(op[0], op[1], op[2], op[3]);
+      reinterpret_cast<uint4*>(a.m)[i] = make_uint4(om[0], om[1], om[2], om[3]);
+      reinterpret_cast<uint4*>(a.v)[i] = make_uint4(ov[0], ov[1], ov[2], ov[3]);
+      if (EMA) {
+        reinterpret_cast<float4*>(x.e)[2 * i] = make_float4(e[0], e[1], e[2], e[3]);
+        reinterpret_cast<float4*>(x.e)[2 * i + 1] = make_float4(e[4], e[5], e[6], e[7]);
+      }
+    }
+    i = nx; id = id_nx;
+  }
+  if (blockIdx.x == 0 && (nvec << 3) < a.n) {      // the ragged tail (n % 8 elements) belongs to the last map byte
+    const unsigned idt = map[nvec];
+    if (idt < (unsigned)n_groups) {
+      const float2 r = rows[idt];
+      for (int64_t j = (nvec << 3) + threadIdx.x; j < a.n; j += 256) {
+        float p = bf2f(a.p[j]), m = bf2f(a.m[j]), v = bf2f(a.v[j]);
+        adam_group_one<true>(p, bf2f(a.g[j]), m, v, a, r.x, r.y, coef);
+        const bf16_t pb = f2bf(p);
+        a.p[j] = pb; a.m[j] = f2bf(m); a.v[j] = f2bf(v);
+        if (EMA) { float e = x.e[j]; ema_one(e, bf2f(pb), x); x.e[j] = e; }
+      }
+    }
+  }
+}
+
 inline unsigned step_blocks(int64_t n) {      // 8 elements per thread, at most 4096 blocks (grid-stride beyond)
   int64_t blocks = (n / 8 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
@@ -755,5 +949,117 @@ extern "C" int dvla_ema_swap_bf16(void* param, const float* ema, void* stash, in
   if (!al16(param) || !al16(ema) || !al16(stash)) return DVLA_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(ema_swap_bf16_kernel, dim3(step_blocks(n)), dim3(256), 0, stream, reinterpret_cast<bf16_t*>(param), ema,
                      reinterpret_cast<bf16_t*>(stash), n, (int)(restore != 0));
+  return dvla_check_launch();
+}
+
+// ---- parameter groups (additive, ABI 9) -------------------------------------------------------------------------------------
+extern "C" int dvla_group_scalars(const double* lr, const double* weight_decay, int32_t n_groups, double beta1, double beta2,
+                                  int64_t base, int32_t n_cand, dvla_group_row* out) {
+  if (!lr || !weight_decay || !out || n_groups < 1 || n_groups > DVLA_STEP_MAX_GROUPS || base < 1 || n_cand < 1 ||
+      n_cand > DVLA_STEP_MAX_CANDIDATES)
+    return DVLA_ERR_ARG;
+  for (int32_t g = 0; g < n_groups; ++g) {
+    out[g].decay = master_decay(lr[g], weight_decay[g]);
+    out[g].lr = (float)lr[g]; out[g].weight_decay = (float)weight_decay[g];      // as dvla_adamw_bf16 receives them
+    float bc2_sqrt;                                                               // common to all groups: not kept here
+    for (int32_t j = 0; j < DVLA_STEP_MAX_CANDIDATES; ++j)
+      master_step_scalars(lr[g], beta1, beta2, base + (j < n_cand ? j : n_cand - 1), &bc2_sqrt, &out[g].step_size[j]);
+  }
+  return DVLA_OK;
+}
+
+namespace {
+
+// what the grouped entry points check alike; returns DVLA_OK when the launch is to go ahead
+inline int grouped_args(bool streams, int64_t n, const void* map, int32_t n_groups, const double* lr, const double* wd, int64_t step,
+                        const dvla_step_state* state, const float* ema, const float* ema_w, int32_t n_cand) {
+  if (!streams || !map || !lr || !wd || n < 0 || step < 1 || n_groups < 1 || n_groups > DVLA_STEP_MAX_GROUPS) return DVLA_ERR_ARG;
+  if (ema && !ema_w) return DVLA_ERR_ARG;
+  if (state && (n_cand < 1 || n_cand > DVLA_STEP_MAX_CANDIDATES)) return DVLA_ERR_ARG;
+  return DVLA_OK;
+}
+
+template <int NC>
+inline void group_tab(GroupTab<NC>& t, const dvla_group_row* rows, int32_t n_groups, bool master) {
+  for (int g = 0; g < DVLA_STEP_MAX_GROUPS; ++g) {
+    const dvla_group_row& r = rows[g < n_groups ? g : n_groups - 1];
+    t.x[g] = master ? r.decay : r.lr;
+    for (int k = 0; k < NC; ++k) t.y[k][g] = master ? r.step_size[k] : r.weight_decay;
+  }
+}
+
+}  // namespace
+
+extern "C" int dvla_adamw_bf16_grouped(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, float* ema, int64_t n,
+                                       const uint8_t* group_map, int32_t n_groups, const double* lr, const double* weight_decay,
+                                       float beta1, float beta2, float eps, int64_t step, const float* grad_sumsq, float max_norm,
+                                       const dvla_step_state* state, const float* ema_w, int32_t n_cand, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  int rc = grouped_args(param && grad && exp_avg && exp_avg_sq, n, group_map, n_groups, lr, weight_decay, step, state, ema, ema_w,
+                        n_cand);
+  if (rc != DVLA_OK) return rc;
+  if (n == 0) return DVLA_OK;
+  if (!al16(param) || !al16(grad) || !al16(exp_avg) || !al16(exp_avg_sq) || (ema && !al16(ema)) || (state && !al16(state)))
+    return DVLA_ERR_UNSUPPORTED;
+  if (!state) n_cand = 1;
+  dvla_group_row rows[DVLA_STEP_MAX_GROUPS];
+  rc = dvla_group_scalars(lr, weight_decay, n_groups, beta1, beta2, step, n_cand, rows);
+  if (rc != DVLA_OK) return rc;
+  AdamArgs a;
+  a.p = reinterpret_cast<bf16_t*>(param); a.g = reinterpret_cast<const bf16_t*>(grad);
+  a.m = reinterpret_cast<bf16_t*>(exp_avg); a.v = reinterpret_cast<bf16_t*>(exp_avg_sq); a.n = n;
+  a.lr = a.wd = 0.f;                          // per group: the kernel takes both from its table
+  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
+  a.inv_bc1 = a.inv_bc2_sqrt = 0.f;           // guarded: the kernel takes both from the state
+  if (!state) bf16_step_scalars(beta1, beta2, step, &a.inv_bc1, &a.inv_bc2_sqrt);
+  a.sumsq = state ? (max_norm > 0.f ? &state->sumsq : nullptr) : grad_sumsq; a.max_norm = max_norm;
+  GroupTab<1> t;
+  group_tab(t, rows, n_groups, false);
+  EmaTable w;
+  if (ema) ema_table(w, ema_w, n_cand); else for (float& x : w.w) x = 0.f;
+  const dim3 grid(step_blocks(n)), block(256);
+  if (state && ema) hipLaunchKernelGGL((adamw_grouped_kernel<true, true>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state);
+  else if (state) hipLaunchKernelGGL((adamw_grouped_kernel<true, false>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state);
+  else if (ema) hipLaunchKernelGGL((adamw_grouped_kernel<false, true>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state);
+  else hipLaunchKernelGGL((adamw_grouped_kernel<false, false>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state);
+  return dvla_check_launch();
+}
+
+extern "C" int dvla_adamw_f32_master_grouped(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
+                                             float* ema, int64_t n, const uint8_t* group_map, int32_t n_groups, const double* lr,
+                                             const double* weight_decay, double beta1, double beta2, double eps, int64_t step,
+                                             const float* grad_sumsq, float max_norm, const dvla_step_state* state,
+                                             const float* ema_w, int32_t n_cand, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  int rc = grouped_args(param && grad && exp_avg && exp_avg_sq, n, group_map, n_groups, lr, weight_decay, step, state, ema, ema_w,
+                        n_cand);
+  if (rc != DVLA_OK) return rc;
+  if (n == 0) return DVLA_OK;
+  if (!al16(param) || !al16(grad) || !al16(exp_avg) || !al16(exp_avg_sq) || (shadow_bf16 && !al16(shadow_bf16)) ||
+      (ema && !al16(ema)) || (state && !al16(state)))
+    return DVLA_ERR_UNSUPPORTED;
+  if (!state) n_cand = 1;
+  dvla_group_row rows[DVLA_STEP_MAX_GROUPS];
+  rc = dvla_group_scalars(lr, weight_decay, n_groups, beta1, beta2, step, n_cand, rows);
+  if (rc != DVLA_OK) return rc;
+  MasterArgs a;
+  a.p = param; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.sh = reinterpret_cast<bf16_t*>(shadow_bf16); a.n = n;
+  master_fixed_scalars(a, lr[0], beta1, beta2, eps, weight_decay[0]);      // decay and step_size: per group, from the table
+  master_step_scalars(lr[0], beta1, beta2, step, &a.bc2_sqrt, &a.step_size);      // guarded: the kernel takes bc2_sqrt from the state
+  a.sumsq = state ? (max_norm > 0.f ? &state->sumsq : nullptr) : grad_sumsq; a.max_norm = max_norm;
+  EmaTable w;
+  if (ema) ema_table(w, ema_w, n_cand); else for (float& x : w.w) x = 0.f;
+  const dim3 grid(step_blocks(n)), block(256);
+  if (state) {
+    GroupTab<DVLA_STEP_MAX_CANDIDATES> t;
+    group_tab(t, rows, n_groups, true);
+    if (ema) hipLaunchKernelGGL((adamw_master_grouped_kernel<true, true>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state);
+    else hipLaunchKernelGGL((adamw_master_grouped_kernel<true, false>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state);
+  } else {
+    GroupTab<1> t;
+    group_tab(t, rows, n_groups, true);
+    if (ema) hipLaunchKernelGGL((adamw_master_grouped_kernel<false, true>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state);
+    else hipLaunchKernelGGL((adamw_master_grouped_kernel<false, false>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state);
+  }
   return dvla_check_launch();
 }

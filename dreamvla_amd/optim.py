@@ -23,6 +23,10 @@ count that is then current, and `dvla_adamw_bf16_guarded` / `dvla_adamw_f32_mast
 EMA of the weights (`ema_decay=...`, an addition): one fp32 EMA buffer per bucket, updated by the step kernels
 themselves (`dvla_adamw_*_ema`, `dvla_adamw_*_ema_guarded`: e <- lerp(e, p, 1 - decay) on the parameter just written, ATen's
 lerp bit for bit), and exchanged with the weights for evaluation by `dvla_ema_swap_f32` / `dvla_ema_swap_bf16`.
+
+Parameter groups (`param_groups=[...]`, an addition): with two or more groups a step is one
+`dvla_adamw_bf16_grouped` / `dvla_adamw_f32_master_grouped` launch per bucket; a map of one byte per 8 elements tells the kernel
+which group's lr and weight decay a vector takes, guard and EMA included.  `weight_decay_groups` builds the usual two groups.
 """
 import collections
 import contextlib
@@ -142,12 +146,21 @@ class FlatAdamW(torch.optim.Optimizer):
     `ema_model_state_dict(model)` the state dict an evaluation script loads; `ema_state_dict()` / `load_ema_state_dict()`
     the checkpoint (state_dict() / load_state_dict() keep their formats and do not touch the EMA); `ema_reset()` restarts
     it from the current parameters.  Under data parallelism every rank steps the same reduced buckets, so every rank holds
-    the same EMA without communication."""
+    the same EMA without communication.
+
+    param_groups=[{"params": [...], "lr": ..., "weight_decay": ...}, ...] (None by default: one group over reducer.params, and the
+    launches above; a list of one group likewise): torch's groups, every parameter of reducer.params in exactly one of them, at
+    most 64, missing keys taken from the constructor; betas and eps are common (ValueError otherwise, here and at step()).
+    `self.param_groups` is the list torch's schedulers write (`LambdaLR(opt, [f0, f1])`), and step() reads every group's lr and
+    weight_decay afresh.  A parameter of group g is stepped exactly -- bit for bit -- as the one-group optimizer with
+    (lr_g, weight_decay_g) steps it; the clip norm stays one norm over everything.  add_param_group raises.  Checkpoints: master
+    mode keeps torch.optim.AdamW's format with several groups (a parameter's index is its position in the concatenation of the
+    groups' lists, torch's numbering); the bf16-only format gains "group_params" (reducer.params indices per group)."""
 
     WINDOW = 8     # guarded steps in flight before step() waits for the oldest readback
 
     def __init__(self, reducer, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, amsgrad=False,
-                 maximize=False, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
+                 maximize=False, skip_nonfinite=False, ema_decay=None, ema_warmup=False, param_groups=None):
         if amsgrad or maximize:
             raise ValueError("FlatAdamW: amsgrad and maximize are not supported")
         if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
@@ -160,8 +173,14 @@ class FlatAdamW(torch.optim.Optimizer):
             raise ValueError(f"FlatAdamW(skip_nonfinite=True): at most {_lib.STEP_MAX_BUCKETS} gradient buckets "
                              f"({len(reducer.buckets)} given)")
         self.reducer = reducer
-        super().__init__(list(reducer.params), dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps),
-                                                    weight_decay=float(weight_decay)))
+        defaults = dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps), weight_decay=float(weight_decay))
+        if param_groups is None:
+            super().__init__(list(reducer.params), defaults)
+        else:       # (copies: torch fills the defaults into the dicts it is given)
+            super().__init__([dict(g) for g in resolve_param_groups(reducer.params, param_groups, defaults)], defaults)
+        self._groups_fixed = True
+        self._group_of = {id(p): gi for gi, g in enumerate(self.param_groups) for p in g["params"]}
+        self._group_maps = {}               # bucket -> (what _stepped(bucket) was, the device map built from it)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.step_count = 0
         self.flat = []
@@ -354,6 +373,8 @@ class FlatAdamW(torch.optim.Optimizer):
     def step(self, closure=None):
         if self._ema_active:
             raise RuntimeError("FlatAdamW.step() inside ema_weights(): the model holds the EMA weights, not the training weights")
+        if len(self.param_groups) > 1:
+            return self._grouped_step()
         if self.skip_nonfinite:
             return self._guarded_step()
         lib = _lib.load()
@@ -405,6 +426,81 @@ class FlatAdamW(torch.optim.Optimizer):
                       "dvla_adamw_bf16")
         if self.master_mode:
             self._publish_shadows()
+
+    def add_param_group(self, param_group):
+        if getattr(self, "_groups_fixed", False):
+            raise RuntimeError("FlatAdamW.add_param_group: the groups are fixed at construction (pass param_groups=[...]); every "
+                               "parameter of the reducer already lives in a flat buffer and belongs to one group")
+        super().add_param_group(param_group)
+
+    def _group_map(self, bi):
+        """the device map of bucket bi (dvla.h: one byte per 8 elements), rebuilt when _stepped(bi) changes -- the reducer learns
+        its unused parameters after the first finish()"""
+        stepped = tuple(bool(u) for u in self._stepped(bi))
+        hit = self._group_maps.get(bi)
+        if hit is None or hit[0] != stepped:
+            b = self.reducer.buckets[bi]
+            cpu = build_group_map(b["offsets"], [p.numel() for p in b["params"]], b["flat"].numel(),
+                                  [self._group_of[id(p)] for p in b["params"]], stepped, len(self.param_groups))
+            hit = (stepped, cpu.to(b["flat"].device))
+            self._group_maps[bi] = hit
+        return hit[1]
+
+    def _grouped_step(self):
+        """step() with two or more parameter groups: one dvla_adamw_*_grouped launch per bucket, guarded or not, with or without
+        the EMA; every group's lr / weight_decay is read afresh.  One clip norm over all buckets and groups."""
+        lib = _lib.load()
+        stream = torch.cuda.current_stream().cuda_stream
+        b1, b2, eps = common_betas_eps(self.param_groups)
+        n_groups = len(self.param_groups)
+        lrs = (ctypes.c_double * n_groups)(*[float(g["lr"]) for g in self.param_groups])
+        wds = (ctypes.c_double * n_groups)(*[float(g["weight_decay"]) for g in self.param_groups])
+        guard, ema, clip = self.skip_nonfinite, self.ema_decay is not None, self.max_grad_norm is not None
+        max_norm = self.max_grad_norm if clip else 0.0      # guarded, <= 0: the norm only feeds the verdict
+        if guard:       # the verdict as in _guarded_step; of its candidates the grouped kernels use what no lr enters
+            confirmed, n_cand = self._ledger.begin()
+            self.step_count = confirmed
+            base, state, sumsq = confirmed + 1, self._state.data_ptr(), None
+            for i, s in enumerate(self.flat):
+                fn = lib.dvla_sumsq_f32 if "sh" in s else lib.dvla_sumsq_bf16
+                check(fn(s["g"].data_ptr(), s["g"].numel(), self._partial.data_ptr(), self._slots.data_ptr() + 4 * i, 0, stream),
+                      "dvla_sumsq")
+            check(lib.dvla_step_candidates(lrs[0], b1, b2, base, n_cand, self._cand), "dvla_step_candidates")
+            check(lib.dvla_step_verdict(self._slots.data_ptr(), len(self.flat), self._sumsq.data_ptr(), state, confirmed, n_cand,
+                                        self._cand, stream), "dvla_step_verdict")
+        else:
+            self.step_count += 1
+            base, n_cand, state, sumsq = self.step_count, 1, None, (self._sumsq.data_ptr() if clip else None)
+            if clip:
+                for i, s in enumerate(self.flat):
+                    fn = lib.dvla_sumsq_f32 if "sh" in s else lib.dvla_sumsq_bf16
+                    check(fn(s["g"].data_ptr(), s["g"].numel(), self._partial.data_ptr(), self._sumsq.data_ptr(), 1 if i > 0 else 0,
+                             stream), "dvla_sumsq")
+        if ema:
+            check(lib.dvla_ema_weights(self.ema_decay, int(self.ema_warmup), base, n_cand, self._ema_w), "dvla_ema_weights")
+        ema_w = self._ema_w if ema else None
+        for bi, s in enumerate(self.flat):
+            if not any(self._stepped(bi)):
+                continue
+            e = s["ema"].data_ptr() if ema else None
+            if "sh" in s:
+                check(lib.dvla_adamw_f32_master_grouped(
+                    s["p"].data_ptr(), s["g"].data_ptr(), s["m"].data_ptr(), s["v"].data_ptr(), s["sh"].data_ptr(), e,
+                    s["p"].numel(), self._group_map(bi).data_ptr(), n_groups, lrs, wds, b1, b2, eps, base, sumsq, max_norm, state,
+                    ema_w, n_cand, stream), "dvla_adamw_f32_master_grouped")
+            else:
+                check(lib.dvla_adamw_bf16_grouped(
+                    s["p"].data_ptr(), s["g"].data_ptr(), s["m"].data_ptr(), s["v"].data_ptr(), e, s["p"].numel(),
+                    self._group_map(bi).data_ptr(), n_groups, lrs, wds, b1, b2, eps, base, sumsq, max_norm, state, ema_w, n_cand,
+                    stream), "dvla_adamw_bf16_grouped")
+        if guard:
+            ticket = self._ring[self._issued % self.WINDOW]       # free: fewer than WINDOW steps are in flight after begin()
+            self._issued += 1
+            ticket.slot.copy_(self._state[:_lib.STEP_READBACK_BYTES], non_blocking=True)
+            ticket.event.record(torch.cuda.current_stream())
+            self._ledger.issued(ticket)
+        if self.master_mode:
+            self._publish_shadows_guarded() if guard else self._publish_shadows()
 
     def _publish_shadows(self):
         """hand the freshly written bf16 copies to dreamvla_amd.ops as the shadows of the stepped masters (recorded at each
@@ -552,13 +648,28 @@ class FlatAdamW(torch.optim.Optimizer):
     def _state_dict(self, step):
         if self.master_mode:
             with_state = [[bool(u) and step > 0 for u in self._stepped(bi)] for bi in range(len(self.flat))]
-            return {"state": torch_state_from_flat(self._layout(), [s["m"] for s in self.flat], [s["v"] for s in self.flat],
+            starts = [sum(len(g["params"]) for g in self.param_groups[:k]) for k in range(len(self.param_groups))]
+            return {"state": torch_state_from_flat(self._torch_layout(), [s["m"] for s in self.flat], [s["v"] for s in self.flat],
                                                    step, with_state),
-                    "param_groups": [_torch_group(g, len(self.reducer.params)) for g in self.param_groups]}
-        return {"step": step,
-                "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups],
-                "layout": [[int(p.numel()) for p in b["params"]] for b in self.reducer.buckets],
-                "exp_avg": [s["m"].clone() for s in self.flat], "exp_avg_sq": [s["v"].clone() for s in self.flat]}
+                    "param_groups": [_torch_group(g, len(g["params"]), k) for g, k in zip(self.param_groups, starts)]}
+        sd = {"step": step,
+              "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups],
+              "layout": [[int(p.numel()) for p in b["params"]] for b in self.reducer.buckets],
+              "exp_avg": [s["m"].clone() for s in self.flat], "exp_avg_sq": [s["v"].clone() for s in self.flat]}
+        if len(self.param_groups) > 1:
+            sd["group_params"] = self._group_params()
+        return sd
+
+    def _group_params(self):
+        """per group: the indices into reducer.params of its parameters"""
+        index = {id(p): i for i, p in enumerate(self.reducer.params)}
+        return [[index[id(p)] for p in g["params"]] for g in self.param_groups]
+
+    def _torch_layout(self):
+        """_layout() with every parameter numbered as torch.optim.Optimizer.state_dict() numbers it: by its position in the
+        concatenation of the groups' `params` lists (with one group over reducer.params that is _layout())"""
+        order = {id(p): i for i, p in enumerate(p for g in self.param_groups for p in g["params"])}
+        return [[(order[id(self.reducer.params[i])], off, shape) for i, off, shape in lay] for lay in self._layout()]
 
     def load_state_dict(self, sd):
         """the inverse of state_dict().  With skip_nonfinite the device's counters and the ledger restart from the loaded step
@@ -573,19 +684,30 @@ class FlatAdamW(torch.optim.Optimizer):
         if self.master_mode:
             groups = sd.get("param_groups") if isinstance(sd, dict) else None
             n = len(self.reducer.params)
-            if "state" not in sd or not groups or len(groups) != 1 or list(groups[0].get("params", ())) != list(range(n)):
+            sizes = [len(g["params"]) for g in self.param_groups]
+            want = [list(range(sum(sizes[:k]), sum(sizes[:k + 1]))) for k in range(len(sizes))]
+            if "state" not in sd or not groups or [list(g.get("params", ())) for g in groups] != want:
+                if len(want) > 1:
+                    raise ValueError(f"FlatAdamW.load_state_dict: expected torch.optim.AdamW's format with {len(want)} parameter "
+                                     f"groups of {sizes} parameters (indices 0..{n - 1} in the order of the groups' lists)")
                 raise ValueError(f"FlatAdamW.load_state_dict: expected torch.optim.AdamW's format with ONE parameter group over "
                                  f"the {n} trainable parameters (indices 0..{n - 1}, reducer.params order)")
-            if groups[0].get("amsgrad") or groups[0].get("maximize"):
+            if any(g.get("amsgrad") or g.get("maximize") for g in groups):
                 raise ValueError("FlatAdamW.load_state_dict: amsgrad / maximize checkpoints are not supported")
-            self.step_count = flat_from_torch_state(self._layout(), sd["state"], [s["m"] for s in self.flat],
+            common_betas_eps(groups)
+            self.step_count = flat_from_torch_state(self._torch_layout(), sd["state"], [s["m"] for s in self.flat],
                                                     [s["v"] for s in self.flat])
-            for k in ("lr", "betas", "eps", "weight_decay"):
-                self.param_groups[0][k] = groups[0][k]
+            for mine, saved in zip(self.param_groups, groups):
+                for k in ("lr", "betas", "eps", "weight_decay"):
+                    mine[k] = saved[k]
             return
         layout = [[int(p.numel()) for p in b["params"]] for b in self.reducer.buckets]
         if sd["layout"] != layout:
             raise ValueError("FlatAdamW.load_state_dict: the checkpoint's bucket layout does not match this model / reducer")
+        mine = self._group_params() if len(self.param_groups) > 1 else None
+        if sd.get("group_params") != mine:
+            raise ValueError(f"FlatAdamW.load_state_dict: the checkpoint's parameter groups (reducer.params indices per group: "
+                             f"{sd.get('group_params')}) are not this optimizer's ({mine})")
         self.step_count = int(sd["step"])
         for g, saved in zip(self.param_groups, sd["param_groups"]):
             g.update(saved)
@@ -601,12 +723,91 @@ def flat_layout(reducer):
     return [[(index[id(p)], off, tuple(p.shape)) for p, off in zip(b["params"], b["offsets"])] for b in reducer.buckets]
 
 
-def _torch_group(g, n):
+def resolve_param_groups(params, param_groups, defaults):
+    """torch-style groups ({"params": [...], "lr": ..., "weight_decay": ...}; missing keys take `defaults`) checked against the
+    reducer's parameter list (pure; works on CPU tensors): every parameter of `params` in exactly one group, nothing else in any,
+    at most DVLA_STEP_MAX_GROUPS groups, betas / eps those of `defaults`.  ValueError names the offender by its position."""
+    groups = [dict(g) for g in param_groups]
+    if not groups or not all("params" in g for g in groups):
+        raise ValueError("FlatAdamW: param_groups must be a non-empty list of dicts with a 'params' list")
+    if len(groups) > _lib.STEP_MAX_GROUPS:
+        raise ValueError(f"FlatAdamW: at most {_lib.STEP_MAX_GROUPS} parameter groups ({len(groups)} given)")
+    index = {id(p): i for i, p in enumerate(params)}
+    owner = {}
+    for gi, g in enumerate(groups):
+        g["params"] = [g["params"]] if isinstance(g["params"], torch.Tensor) else list(g["params"])
+        for k, p in enumerate(g["params"]):
+            if id(p) not in index:
+                raise ValueError(f"FlatAdamW: parameter {k} of group {gi} (shape {tuple(p.shape)}) is not a parameter of the reducer")
+            if id(p) in owner:
+                raise ValueError(f"FlatAdamW: parameter {index[id(p)]} of reducer.params (shape {tuple(p.shape)}) is in two groups "
+                                 f"({owner[id(p)]} and {gi})")
+            owner[id(p)] = gi
+        for key in ("betas", "eps"):
+            if key in g and _hyper(g[key]) != _hyper(defaults[key]):
+                raise ValueError(f"FlatAdamW: group {gi} has {key} = {g[key]!r}, the optimizer {defaults[key]!r}: betas and eps "
+                                 f"are common to all groups (the bias corrections depend on them)")
+    for i, p in enumerate(params):
+        if id(p) not in owner:
+            raise ValueError(f"FlatAdamW: parameter {i} of reducer.params (shape {tuple(p.shape)}) is in no group")
+    return groups
+
+
+def _hyper(x):
+    return tuple(float(v) for v in x) if isinstance(x, (tuple, list)) else float(x)
+
+
+def common_betas_eps(groups):
+    """(beta1, beta2, eps) of group 0, which every group must share (ValueError: someone edited one group's)"""
+    betas, eps = _hyper(groups[0]["betas"]), _hyper(groups[0]["eps"])
+    for gi, g in enumerate(groups):
+        if _hyper(g["betas"]) != betas or _hyper(g["eps"]) != eps:
+            raise ValueError(f"FlatAdamW: group {gi} has betas = {g['betas']!r}, eps = {g['eps']!r}, group 0 {groups[0]['betas']!r}, "
+                             f"{groups[0]['eps']!r}: betas and eps are common to all groups")
+    return betas[0], betas[1], eps
+
+
+def build_group_map(offsets, sizes, total, group_ids, stepped, n_groups):
+    """the group map of one bucket (include/dvla.h; pure): a CPU uint8 tensor of ceil(total / 8) bytes, one per vector of 8
+    elements.  Parameter j occupies elements offsets[j] .. offsets[j] + sizes[j]; its vectors (the last one may be partial, and
+    may be the bucket's ragged tail) get group_ids[j] if stepped[j], everything else -- parameters the step leaves alone,
+    alignment gaps -- 255.  Parameters start on multiples of 8 elements, so no vector belongs to two of them."""
+    out = torch.full(((int(total) + 7) // 8,), 255, dtype=torch.uint8)
+    for off, n, gid, used in zip(offsets, sizes, group_ids, stepped):
+        if off % 8:
+            raise ValueError(f"FlatAdamW: a parameter starts at element {off} of its bucket, not on a multiple of 8")
+        if not 0 <= gid < n_groups or gid >= 255:
+            raise ValueError(f"FlatAdamW: group id {gid} outside 0 .. {n_groups - 1}")
+        if off + n > total:
+            raise ValueError(f"FlatAdamW: a parameter ends at element {off + n} of a bucket of {total}")
+        if used and n > 0:
+            out[off // 8:(off + n + 7) // 8] = gid
+    return out
+
+
+def weight_decay_groups(module_or_named_parameters, weight_decay, skip=()):
+    """The two parameter groups of the usual rule, as plain torch groups (for FlatAdamW(param_groups=...) and torch.optim.AdamW
+    alike): weight_decay = 0.0 for trainable parameters with ndim <= 1 (biases, LayerNorm weights), a name ending in ".bias" or
+    a name in `skip` (cls_token, pos_embed, ... of a ViT); `weight_decay` for every other trainable parameter.  Frozen parameters
+    are left out; a group that would be empty is omitted.  -> [no-decay group, decay group]"""
+    named = module_or_named_parameters
+    named = named.named_parameters() if hasattr(named, "named_parameters") else named
+    skip = set(skip)
+    plain, decayed = [], []
+    for name, p in named:
+        if not p.requires_grad:
+            continue
+        (plain if p.ndim <= 1 or name.endswith(".bias") or name in skip else decayed).append(p)
+    groups = [{"params": plain, "weight_decay": 0.0}, {"params": decayed, "weight_decay": float(weight_decay)}]
+    return [g for g in groups if g["params"]]
+
+
+def _torch_group(g, n, start=0):
     """a parameter group as torch.optim.AdamW.state_dict() writes it (every key its load_state_dict expects)"""
     out = {"lr": g["lr"], "betas": tuple(g["betas"]), "eps": g["eps"], "weight_decay": g["weight_decay"], "amsgrad": False,
            "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
            "decoupled_weight_decay": True}
-    out["params"] = list(range(n))
+    out["params"] = list(range(start, start + n))
     return out
 
 

@@ -468,6 +468,40 @@ int dvla_adamw_f32_master_ema_guarded(float* param, const float* grad, float* ex
                                       int32_t n_cand, void* stream);
 int dvla_ema_swap_f32(float* param, float* ema, void* shadow_bf16, int64_t n, void* stream);
 int dvla_ema_swap_bf16(void* param, const float* ema, void* stash, int64_t n, int32_t restore, void* stream);
+/* (additive, ABI 9) Parameter groups: per-group lr and weight decay in ONE launch per bucket whatever the number
+ * of groups; betas, eps and the clip coefficient stay common.  A parameter of group g comes out bit-identical to that
+ * parameter under the one-group entry points called with (lr[g], weight_decay[g]).
+ * group_map: device memory, one byte per vector of 8 elements, (n + 7) / 8 bytes: a group id 0 .. n_groups - 1, or 255 = leave
+ *   this vector alone (nothing of it is read or written: parameter, moments, shadow and EMA keep their bits).  The n % 8 ragged
+ *   tail belongs to the last byte.  Ids in n_groups .. 254 are the caller's error (check them where the map is built); the
+ *   kernels treat them as 255.
+ * lr, weight_decay: HOST arrays of n_groups doubles.  The kernels receive floats derived from them by value (no upload):
+ * dvla_group_scalars: no launch; the one place they are derived, with the expressions of the one-group entry points.
+ *   out[g].decay = (float)(1 - lr weight_decay) and out[g].step_size[j] = (float)((lr / (1 - beta1^(base + j))) * -1.0), j < n_cand
+ *   (dvla_adamw_f32_master's; step_size[j] is what dvla_step_candidates(lr[g], ...) gives; rows j >= n_cand repeat the last);
+ *   out[g].lr, out[g].weight_decay = the doubles rounded to float (dvla_adamw_bf16's arguments).
+ * dvla_adamw_bf16_grouped / dvla_adamw_f32_master_grouped: the streams of dvla_adamw_bf16 / dvla_adamw_f32_master, + `ema`
+ *   (n floats, or NULL: no EMA) and `state` (or NULL: no guard).
+ *   state == NULL: `step` is the 1-based step count, grad_sumsq as in the twin, ema_w[0] the EMA weight; n_cand is ignored.
+ *   state != NULL: the guarded step.  `step` is the `base` and n_cand the count given to dvla_step_candidates / dvla_step_verdict,
+ *     ema_w the host table of n_cand weights; the gradient is clipped on state->sumsq iff max_norm > 0 (grad_sumsq is ignored);
+ *     state->ok == 0: nothing is read or written.
+ * DVLA_ERR_ARG: a null pointer (ema_w with ema != NULL included), n < 0, step < 1, n_groups outside 1 .. DVLA_STEP_MAX_GROUPS,
+ *   n_cand outside 1 .. DVLA_STEP_MAX_CANDIDATES.  DVLA_ERR_UNSUPPORTED: a base that is not 16-byte aligned (the map may sit at
+ *   any address).  n == 0: DVLA_OK, nothing launched. */
+#define DVLA_STEP_MAX_GROUPS 64
+typedef struct dvla_group_row { float decay, lr, weight_decay; float step_size[DVLA_STEP_MAX_CANDIDATES]; } dvla_group_row;
+int dvla_group_scalars(const double* lr, const double* weight_decay, int32_t n_groups, double beta1, double beta2, int64_t base,
+                       int32_t n_cand, dvla_group_row* out);
+int dvla_adamw_bf16_grouped(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, float* ema, int64_t n,
+                            const uint8_t* group_map, int32_t n_groups, const double* lr, const double* weight_decay, float beta1,
+                            float beta2, float eps, int64_t step, const float* grad_sumsq, float max_norm,
+                            const dvla_step_state* state, const float* ema_w, int32_t n_cand, void* stream);
+int dvla_adamw_f32_master_grouped(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, float* ema,
+                                  int64_t n, const uint8_t* group_map, int32_t n_groups, const double* lr,
+                                  const double* weight_decay, double beta1, double beta2, double eps, int64_t step,
+                                  const float* grad_sumsq, float max_norm, const dvla_step_state* state, const float* ema_w,
+                                  int32_t n_cand, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Token assembly (models/dreamvla_model.py:739-759): out[b, s, t, :] = part_k[b, s, t - tok_begin_k, :] + pos[s, :]
