@@ -215,6 +215,10 @@ SYMBOLS = {
     "dvla_adamw_f32_master_grouped": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _P, _I32, C.POINTER(C.c_double),
                                                 C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, _I64, _P, C.c_float, _P,
                                                 C.POINTER(C.c_float), _I32, _P]),
+    "dvla_sr_cast_f32_to_bf16": (C.c_int, [_P, _P, _I64, C.c_uint64, C.c_uint64, _I32, _I32, _I64, _P]),
+    "dvla_adamw_bf16_sr": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P, _I32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                     C.c_float, C.c_float, C.c_float, _I64, _P, C.c_float, _P, C.POINTER(C.c_float), _I32,
+                                     C.c_uint64, _I32, _I64, _P]),
 }
 
 _lib = None

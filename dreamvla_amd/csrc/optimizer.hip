@@ -27,6 +27,11 @@
 //   dvla_adamw_*_ema(_guarded)    : the four AdamW kernels + e <- lerp(e, p, w) on the parameter just written (ATen's lerp, bit for
 //                                   bit): 30 + 8 = 38 B / parameter on fp32 masters, 14 + 8 = 22 B on bf16; w from dvla_ema_weights
 //   dvla_ema_swap_f32 / _bf16     : the EMA becomes the weights and back (evaluation), the bf16 shadow written in the same pass
+//
+// stochastic rounding (an addition; dvla.h): pure bf16 with round-to-nearest stores cannot train,
+//   dvla_adamw_bf16_sr            : the bf16 step -- plain, guarded, with the EMA, grouped -- with parameter and both moments rounded
+//                                   up with a probability equal to the discarded fraction, from counter-based random bits: 14 B still
+//   dvla_sr_cast_f32_to_bf16      : the same rounding and bits as a stand-alone cast
 #include "common.h"
 #include "../../include/dvla.h"
 
@@ -690,6 +695,127 @@ __global__ __launch_bounds__(256) void adamw_grouped_kernel(AdamArgs a, const ui
   }
 }
 
+// ---- stochastic rounding of the bf16 stores (additive; dvla.h) --------------------------------------------------
+// The generator and the rounding as dvla.h states them (tests/sr_ref.py restates both in integer arithmetic): 16 random bits per
+// stored value from two hashes per element, keyed by (seed, applied step count, bucket) and the element's index in its bucket.
+__device__ __forceinline__ uint32_t sr_bf16(uint32_t u, uint32_t r) {      // u: the fp32 bits, r: 16 random bits -> the bf16 bits
+  if ((u & 0x7f800000u) == 0x7f800000u) return (u >> 16) | ((u & 0x007fffffu) ? 0x0040u : 0u);      // inf stays, NaN stays NaN
+  return (u + r) >> 16;
+}
+__device__ __forceinline__ uint32_t sr_key(uint64_t seed, uint64_t step, uint32_t bucket) {
+  uint32_t k = hash32((uint32_t)seed ^ 0x243F6A88u);
+  k = hash32(k ^ (uint32_t)(seed >> 32));
+  k = hash32(k ^ (uint32_t)step);
+  k = hash32(k ^ (uint32_t)(step >> 32));
+  return hash32(k ^ bucket);
+}
+__device__ __forceinline__ uint32_t sr_hash(uint32_t key, int64_t i) {
+  return hash32((key ^ ((uint32_t)((uint64_t)i >> 32) * 0x85EBCA6Bu)) + (uint32_t)i * 0x9E3779B9u);
+}
+__device__ __forceinline__ uint32_t sr_draw(uint32_t h, int stream) {      // stream 0: param, 1: exp_avg, 2: exp_avg_sq
+  return stream == 0 ? h >> 16 : stream == 1 ? h & 0xffffu : hash32(h ^ 0x5BD1E995u) >> 16;
+}
+// the three stores of element i
+__device__ __forceinline__ void sr_round3(float p, float m, float v, uint32_t key, int64_t i, uint32_t& pb, uint32_t& mb,
+                                          uint32_t& vb) {
+  const uint32_t h = sr_hash(key, i);
+  pb = sr_bf16(__float_as_uint(p), sr_draw(h, 0));
+  mb = sr_bf16(__float_as_uint(m), sr_draw(h, 1));
+  vb = sr_bf16(__float_as_uint(v), sr_draw(h, 2));
+}
+
+__global__ __launch_bounds__(256) void sr_cast_kernel(const float* __restrict__ x, bf16_t* __restrict__ out, int64_t n, uint64_t seed,
+                                                      uint64_t step, uint32_t bucket, int stream, int64_t base) {
+  const uint32_t key = sr_key(seed, step, bucket);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    out[i] = (bf16_t)sr_bf16(__float_as_uint(x[i]), sr_draw(sr_hash(key, base + i), stream));
+}
+
+struct SrArgs { uint64_t seed; int64_t step, base; uint32_t bucket; };      // step: unguarded; base: the index of element 0
+
+// adamw_grouped_kernel with the three final conversions rounded stochastically: the same element function (adam_group_one, so
+// the fp32 values are those of every other bf16 step kernel), the same guard, EMA (on the parameter as stored) and map.
+// MAP false: no map, one group (row 0 of the table) over all n elements -- the one-group step over a range of a bucket.
+template <bool GUARD, bool EMA, bool MAP>
+__global__ __launch_bounds__(256) void adamw_sr_kernel(AdamArgs a, const uint8_t* __restrict__ map, int n_groups, GroupTab<1> t,
+                                                       float* ema, EmaTable wt, const dvla_step_state* __restrict__ st, SrArgs sr) {
+  __shared__ float2 rows[DVLA_STEP_MAX_GROUPS];
+  int cand = 0;
+  if (GUARD) {
+    if (st->ok == 0) return;
+    a.inv_bc1 = st->inv_bc1; a.inv_bc2_sqrt = st->inv_bc2_sqrt;
+    cand = st->cand;
+  }
+  const uint32_t key = sr_key(sr.seed, GUARD ? (uint64_t)st->applied : (uint64_t)sr.step, sr.bucket);
+  if (MAP) {
+    if (threadIdx.x < DVLA_STEP_MAX_GROUPS) rows[threadIdx.x] = group_row(t, n_groups, 0);
+    __syncthreads();
+  }
+  const float2 r0 = make_float2(t.x[0], t.y[0][0]);
+  const EmaArgs x = ema_args(ema, EMA ? ema_pick(wt, cand) : 0.f);
+  const float coef = clip_coef(a.sumsq, a.max_norm);
+  const int64_t nvec = a.n >> 3, stride = (int64_t)gridDim.x * 256;
+  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  unsigned id = 0;
+  if (MAP) id = i < nvec ? map[i] : 255u;
+  while (i < nvec) {
+    const int64_t nx = i + stride;
+    unsigned id_nx = 0;
+    if (MAP) id_nx = nx < nvec ? map[nx] : 255u;
+    if (id < (unsigned)n_groups) {
+      const float2 r = MAP ? rows[id] : r0;      // lr, wd
+      const uint4 up = reinterpret_cast<const uint4*>(a.p)[i], ug = reinterpret_cast<const uint4*>(a.g)[i];
+      const uint4 um = reinterpret_cast<const uint4*>(a.m)[i], uv = reinterpret_cast<const uint4*>(a.v)[i];
+      float4 e0, e1;
+      if (EMA) { e0 = reinterpret_cast<const float4*>(x.e)[2 * i]; e1 = reinterpret_cast<const float4*>(x.e)[2 * i + 1]; }
+      const uint32_t wp[4] = {up.x, up.y, up.z, up.w}, wg[4] = {ug.x, ug.y, ug.z, ug.w};
+      const uint32_t wm[4] = {um.x, um.y, um.z, um.w}, wv[4] = {uv.x, uv.y, uv.z, uv.w};
+      uint32_t op[4], om[4], ov[4];
+      float e[8];
+      if (EMA) { e[0] = e0.x; e[1] = e0.y; e[2] = e0.z; e[3] = e0.w; e[4] = e1.x; e[5] = e1.y; e[6] = e1.z; e[7] = e1.w; }
+      const int64_t el = sr.base + (i << 3);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float p0 = bf2f((bf16_t)(wp[k] & 0xffff)), p1 = bf2f((bf16_t)(wp[k] >> 16));
+        float m0 = bf2f((bf16_t)(wm[k] & 0xffff)), m1 = bf2f((bf16_t)(wm[k] >> 16));
+        float v0 = bf2f((bf16_t)(wv[k] & 0xffff)), v1 = bf2f((bf16_t)(wv[k] >> 16));
+        adam_group_one<false>(p0, bf2f((bf16_t)(wg[k] & 0xffff)), m0, v0, a, r.x, r.y, coef);
+        adam_group_one<false>(p1, bf2f((bf16_t)(wg[k] >> 16)), m1, v1, a, r.x, r.y, coef);
+        uint32_t pb0, mb0, vb0, pb1, mb1, vb1;
+        sr_round3(p0, m0, v0, key, el + 2 * k, pb0, mb0, vb0);
+        sr_round3(p1, m1, v1, key, el + 2 * k + 1, pb1, mb1, vb1);
+        op[k] = pb0 | (pb1 << 16); om[k] = mb0 | (mb1 << 16); ov[k] = vb0 | (vb1 << 16);
+        if (EMA) {      // the EMA follows the bf16 value that is written
+          ema_one(e[2 * k], bf2f((bf16_t)pb0), x);
+          ema_one(e[2 * k + 1], bf2f((bf16_t)pb1), x);
+        }
+      }
+      reinterpret_cast<uint4*>(a.p)[i] = make_uint4(op[0], op[1], op[2], op[3]);
+      reinterpret_cast<uint4*>(a.m)[i] = make_uint4(om[0], om[1], om[2], om[3]);
+      reinterpret_cast<uint4*>(a.v)[i] = make_uint4(ov[0], ov[1], ov[2], ov[3]);
+      if (EMA) {
+        reinterpret_cast<float4*>(x.e)[2 * i] = make_float4(e[0], e[1], e[2], e[3]);
+        reinterpret_cast<float4*>(x.e)[2 * i + 1] = make_float4(e[4], e[5], e[6], e[7]);
+      }
+    }
+    i = nx; id = id_nx;
+  }
+  if (blockIdx.x == 0 && (nvec << 3) < a.n) {      // the ragged tail (n % 8 elements) belongs to the last map byte
+    const unsigned idt = MAP ? map[nvec] : 0u;
+    if (idt < (unsigned)n_groups) {
+      const float2 r = MAP ? rows[idt] : r0;
+      for (int64_t j = (nvec << 3) + threadIdx.x; j < a.n; j += 256) {
+        float p = bf2f(a.p[j]), m = bf2f(a.m[j]), v = bf2f(a.v[j]);
+        adam_group_one<true>(p, bf2f(a.g[j]), m, v, a, r.x, r.y, coef);
+        uint32_t pb, mb, vb;
+        sr_round3(p, m, v, key, sr.base + j, pb, mb, vb);
+        a.p[j] = (bf16_t)pb; a.m[j] = (bf16_t)mb; a.v[j] = (bf16_t)vb;
+        if (EMA) { float e = x.e[j]; ema_one(e, bf2f((bf16_t)pb), x); x.e[j] = e; }
+      }
+    }
+  }
+}
+
 inline unsigned step_blocks(int64_t n) {      // 8 elements per thread, at most 4096 blocks (grid-stride beyond)
   int64_t blocks = (n / 8 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
@@ -1061,5 +1187,68 @@ extern "C" int dvla_adamw_f32_master_grouped(float* param, const float* grad, fl
     if (ema) hipLaunchKernelGGL((adamw_master_grouped_kernel<false, true>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state);
     else hipLaunchKernelGGL((adamw_master_grouped_kernel<false, false>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state);
   }
+  return dvla_check_launch();
+}
+
+// ---- stochastic rounding (additive, ABI 9) ----------------------------------------------------------------------------------
+extern "C" int dvla_sr_cast_f32_to_bf16(const float* x, void* out, int64_t n, uint64_t seed, uint64_t step, int32_t bucket,
+                                        int32_t stream_id, int64_t index_base, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (!x || !out || n < 0 || stream_id < 0 || stream_id > 2) return DVLA_ERR_ARG;
+  if (n == 0) return DVLA_OK;
+  int64_t blocks = (n + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(sr_cast_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, reinterpret_cast<bf16_t*>(out), n, seed, step,
+                     (uint32_t)bucket, (int)stream_id, index_base);
+  return dvla_check_launch();
+}
+
+extern "C" int dvla_adamw_bf16_sr(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, float* ema, int64_t n,
+                                  const uint8_t* group_map, int32_t n_groups, const double* lr, const double* weight_decay,
+                                  float beta1, float beta2, float eps, int64_t step, const float* grad_sumsq, float max_norm,
+                                  const dvla_step_state* state, const float* ema_w, int32_t n_cand, uint64_t sr_seed,
+                                  int32_t sr_bucket, int64_t sr_index_base, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  static const uint8_t no_map = 0;      // grouped_args wants a map; without one there is one group
+  if (!group_map && n_groups != 1) return DVLA_ERR_ARG;
+  int rc = grouped_args(param && grad && exp_avg && exp_avg_sq, n, group_map ? group_map : &no_map, n_groups, lr, weight_decay, step,
+                        state, ema, ema_w, n_cand);
+  if (rc != DVLA_OK) return rc;
+  if (sr_index_base < 0) return DVLA_ERR_ARG;
+  if (n == 0) return DVLA_OK;
+  if (!al16(param) || !al16(grad) || !al16(exp_avg) || !al16(exp_avg_sq) || (ema && !al16(ema)) || (state && !al16(state)))
+    return DVLA_ERR_UNSUPPORTED;
+  if (!state) n_cand = 1;
+  dvla_group_row rows[DVLA_STEP_MAX_GROUPS];
+  rc = dvla_group_scalars(lr, weight_decay, n_groups, beta1, beta2, step, n_cand, rows);
+  if (rc != DVLA_OK) return rc;
+  AdamArgs a;
+  a.p = reinterpret_cast<bf16_t*>(param); a.g = reinterpret_cast<const bf16_t*>(grad);
+  a.m = reinterpret_cast<bf16_t*>(exp_avg); a.v = reinterpret_cast<bf16_t*>(exp_avg_sq); a.n = n;
+  a.lr = a.wd = 0.f;                          // per group: the kernel takes both from its table
+  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
+  a.inv_bc1 = a.inv_bc2_sqrt = 0.f;           // guarded: the kernel takes both from the state
+  if (!state) bf16_step_scalars(beta1, beta2, step, &a.inv_bc1, &a.inv_bc2_sqrt);
+  a.sumsq = state ? (max_norm > 0.f ? &state->sumsq : nullptr) : grad_sumsq; a.max_norm = max_norm;
+  GroupTab<1> t;
+  group_tab(t, rows, n_groups, false);
+  EmaTable w;
+  if (ema) ema_table(w, ema_w, n_cand); else for (float& x : w.w) x = 0.f;
+  SrArgs sr;
+  sr.seed = sr_seed; sr.step = step; sr.base = sr_index_base; sr.bucket = (uint32_t)sr_bucket;
+  const dim3 grid(step_blocks(n)), block(256);
+#define DVLA_SR_LAUNCH(G, E, M)                                                                                                \
+  hipLaunchKernelGGL((adamw_sr_kernel<G, E, M>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state, sr)
+  switch ((state ? 4 : 0) | (ema ? 2 : 0) | (group_map ? 1 : 0)) {
+    case 0: DVLA_SR_LAUNCH(false, false, false); break;
+    case 1: DVLA_SR_LAUNCH(false, false, true); break;
+    case 2: DVLA_SR_LAUNCH(false, true, false); break;
+    case 3: DVLA_SR_LAUNCH(false, true, true); break;
+    case 4: DVLA_SR_LAUNCH(true, false, false); break;
+    case 5: DVLA_SR_LAUNCH(true, false, true); break;
+    case 6: DVLA_SR_LAUNCH(true, true, false); break;
+    default: DVLA_SR_LAUNCH(true, true, true); break;
+  }
+#undef DVLA_SR_LAUNCH
   return dvla_check_launch();
 }

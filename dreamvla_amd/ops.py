@@ -531,6 +531,21 @@ def cast_to(x, dtype):
     return out
 
 
+def stochastic_round_bf16(x, *, seed=0, step=0, bucket=0, stream=0, index_base=0):
+    """fp32 -> bf16 rounded stochastically (dvla_sr_cast_f32_to_bf16; include/dvla.h states the rounding and the counter-based
+    generator): every value is its fp32 value in expectation.  Element j of the flattened x draws stream `stream` (0, 1 or 2)
+    of element index index_base + j under (seed, step, bucket) -- the bits FlatAdamW(stochastic_rounding=True) draws for that
+    element of a bucket.  Turns fp32 masters into a bf16 model, say."""
+    lib = _lib.load()
+    if x.dtype != torch.float32 or not x.is_cuda:
+        raise TypeError(f"stochastic_round_bf16: a CUDA fp32 tensor, got {x.dtype} on {x.device}")
+    x = x.contiguous()
+    out = torch.empty(x.shape, dtype=BF16, device=x.device)
+    check(lib.dvla_sr_cast_f32_to_bf16(x.data_ptr(), out.data_ptr(), x.numel(), int(seed), int(step), int(bucket), int(stream),
+                                       int(index_base), _stream()), "dvla_sr_cast_f32_to_bf16")
+    return out
+
+
 def act_bwd_raw(dy2, preact2, act, dropout_p=0.0, seed=(0, 0)):
     lib = _lib.load()
     if dy2.stride(1) != 1 or dy2.stride(0) != dy2.shape[1]:

@@ -27,17 +27,25 @@ lerp bit for bit), and exchanged with the weights for evaluation by `dvla_ema_sw
 Parameter groups (`param_groups=[...]`, an addition): with two or more groups a step is one
 `dvla_adamw_bf16_grouped` / `dvla_adamw_f32_master_grouped` launch per bucket; a map of one byte per 8 elements tells the kernel
 which group's lr and weight decay a vector takes, guard and EMA included.  `weight_decay_groups` builds the usual two groups.
+
+Stochastic rounding (`stochastic_rounding=True`, an addition): bf16 buckets are stepped by `dvla_adamw_bf16_sr`,
+which stores parameters and both moments rounded up with a probability equal to the discarded fraction, from counter-based random
+bits (include/dvla.h); launch for launch the step of the same combination of guard, EMA and groups.
 """
 import collections
 import contextlib
 import ctypes
 import math
+import operator
 import warnings
 
 import torch
 
 from . import _lib, ops
 from ._lib import check
+
+
+_ONE_DOUBLE = ctypes.c_double * 1      # the one-group (lr, weight_decay) as dvla_adamw_bf16_sr takes them
 
 
 class _StepLedger:
@@ -155,16 +163,36 @@ class FlatAdamW(torch.optim.Optimizer):
     weight_decay afresh.  A parameter of group g is stepped exactly -- bit for bit -- as the one-group optimizer with
     (lr_g, weight_decay_g) steps it; the clip norm stays one norm over everything.  add_param_group raises.  Checkpoints: master
     mode keeps torch.optim.AdamW's format with several groups (a parameter's index is its position in the concatenation of the
-    groups' lists, torch's numbering); the bf16-only format gains "group_params" (reducer.params indices per group)."""
+    groups' lists, torch's numbering); the bf16-only format gains "group_params" (reducer.params indices per group).
+
+    stochastic_rounding=True (off by default; nothing above changes with it off), sr_seed=s, an integer in [0, 2^64): the three
+    bf16 stores of a bf16 bucket's step -- parameter and both moments -- are rounded stochastically instead of to nearest: up in
+    magnitude with a probability equal to the discarded fraction, so every stored value is its fp32 value in expectation.  With
+    round-to-nearest a bf16 weight with |p| > 512 lr never moves and exp_avg_sq never decays at beta2 = 0.999; with
+    this flag the pure-bf16 mode trains at the same 14 B per parameter.  The fp32 arithmetic is that of the step without the flag;
+    the clipped gradient is still rounded to nearest; fp32 master buckets of a mixed reducer are stepped as without the flag (a
+    reducer with no bf16 bucket raises ValueError); the EMA follows the parameter as stored.  Works with skip_nonfinite, ema_decay
+    and param_groups in any combination, at the launch count of that combination.  The random bits are a pure function of
+    (sr_seed, the count of applied steps, the bucket's index, the element's offset in the bucket) -- nothing depends on the rank,
+    the grid or how a bucket is split into ranges -- so ranks that pass the same sr_seed (they must; the default does) hold the
+    same weights with no communication, a skipped step draws nothing, and a run resumed from state_dict() continues bit for bit:
+    the checkpoint carries the seed ("stochastic_rounding": {"seed": s}; in master-mode format inside param_groups[0]), and
+    load_state_dict() takes it over (a checkpoint without it leaves the constructor's seed)."""
 
     WINDOW = 8     # guarded steps in flight before step() waits for the oldest readback
 
     def __init__(self, reducer, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, amsgrad=False,
-                 maximize=False, skip_nonfinite=False, ema_decay=None, ema_warmup=False, param_groups=None):
+                 maximize=False, skip_nonfinite=False, ema_decay=None, ema_warmup=False, param_groups=None, stochastic_rounding=False,
+                 sr_seed=0):
         if amsgrad or maximize:
             raise ValueError("FlatAdamW: amsgrad and maximize are not supported")
         if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
             raise ValueError(f"FlatAdamW: ema_decay must lie strictly between 0 and 1 ({ema_decay!r} given)")
+        self.stochastic_rounding = bool(stochastic_rounding)
+        self.sr_seed = _sr_seed(sr_seed)
+        if self.stochastic_rounding and not any(b["flat"].dtype == torch.bfloat16 for b in reducer.buckets):
+            raise ValueError("FlatAdamW(stochastic_rounding=True): the reducer has no bf16 bucket, so there is nothing to round "
+                             "(fp32 masters are stored exactly)")
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.ema_warmup = bool(ema_warmup)
         self._ema_active = False            # inside ema_weights()
@@ -248,6 +276,16 @@ class FlatAdamW(torch.optim.Optimizer):
             return [False] * len(b["params"])
         return b["expected"]
 
+    def _sr_launch(self, lib, bi, lo, hi, gmap, lrs, wds, b1, b2, eps, step, sumsq, max_norm, state, ema_w, n_cand, stream):
+        """elements lo .. hi of bf16 bucket bi through dvla_adamw_bf16_sr: the plain / guarded / EMA / grouped step of a bf16
+        bucket (gmap None: one group) with stochastically rounded stores; the element index of the random bits starts at lo"""
+        s = self.flat[bi]
+        o = 2 * lo
+        check(lib.dvla_adamw_bf16_sr(s["p"].data_ptr() + o, s["g"].data_ptr() + o, s["m"].data_ptr() + o, s["v"].data_ptr() + o,
+                                     s["ema"].data_ptr() + 4 * lo if ema_w is not None else None, hi - lo, gmap, len(lrs), lrs, wds,
+                                     float(b1), float(b2), eps, step, sumsq, max_norm, state, ema_w, n_cand, self.sr_seed, bi, lo,
+                                     stream), "dvla_adamw_bf16_sr")
+
     @torch.no_grad()
     def _guarded_step(self):
         lib = _lib.load()
@@ -271,6 +309,10 @@ class FlatAdamW(torch.optim.Optimizer):
         for bi, s in enumerate(self.flat):
             for (lo, hi) in self._ranges(bi):
                 if hi <= lo:
+                    continue
+                if self.stochastic_rounding and "sh" not in s:
+                    self._sr_launch(lib, bi, lo, hi, None, _ONE_DOUBLE(lr), _ONE_DOUBLE(wd), b1, b2, eps, confirmed + 1, None,
+                                    max_norm, state, self._ema_w if ema else None, n_cand, stream)
                     continue
                 if ema and "sh" in s:
                     o = 4 * lo
@@ -395,6 +437,11 @@ class FlatAdamW(torch.optim.Optimizer):
             for (lo, hi) in self._ranges(bi):
                 if hi <= lo:
                     continue
+                if self.stochastic_rounding and "sh" not in s:
+                    self._sr_launch(lib, bi, lo, hi, None, _ONE_DOUBLE(lr), _ONE_DOUBLE(wd), b1, b2, eps, self.step_count,
+                                    self._sumsq.data_ptr() if clip else None, self.max_grad_norm if clip else 0.0, None,
+                                    self._ema_w if ema else None, 1, stream)
+                    continue
                 if ema and "sh" in s:
                     o = 4 * lo
                     check(lib.dvla_adamw_f32_master_ema(
@@ -488,6 +535,9 @@ class FlatAdamW(torch.optim.Optimizer):
                     s["p"].data_ptr(), s["g"].data_ptr(), s["m"].data_ptr(), s["v"].data_ptr(), s["sh"].data_ptr(), e,
                     s["p"].numel(), self._group_map(bi).data_ptr(), n_groups, lrs, wds, b1, b2, eps, base, sumsq, max_norm, state,
                     ema_w, n_cand, stream), "dvla_adamw_f32_master_grouped")
+            elif self.stochastic_rounding:
+                self._sr_launch(lib, bi, 0, s["p"].numel(), self._group_map(bi).data_ptr(), lrs, wds, b1, b2, eps, base, sumsq,
+                                max_norm, state, ema_w, n_cand, stream)
             else:
                 check(lib.dvla_adamw_bf16_grouped(
                     s["p"].data_ptr(), s["g"].data_ptr(), s["m"].data_ptr(), s["v"].data_ptr(), e, s["p"].numel(),
@@ -638,12 +688,16 @@ class FlatAdamW(torch.optim.Optimizer):
     def state_dict(self):
         """master mode: torch.optim.AdamW's format (see torch_state_from_flat).  bf16 buckets only: step count, hyper-parameters
         and both moments (flat, per bucket) + the layout they belong to.  With skip_nonfinite the stored step is the number of
-        APPLIED steps (this waits for every enqueued step) and param_groups[0]["skipped_steps"] is added."""
+        APPLIED steps (this waits for every enqueued step) and param_groups[0]["skipped_steps"] is added.  With
+        stochastic_rounding "stochastic_rounding": {"seed": sr_seed} is added (master mode: to param_groups[0])."""
         if self.skip_nonfinite:
             sd = self._state_dict(self.applied_steps)
             sd["param_groups"][0]["skipped_steps"] = self._ledger.confirmed_skipped
-            return sd
-        return self._state_dict(self.step_count)
+        else:
+            sd = self._state_dict(self.step_count)
+        if self.stochastic_rounding:
+            (sd["param_groups"][0] if self.master_mode else sd)["stochastic_rounding"] = {"seed": self.sr_seed}
+        return sd
 
     def _state_dict(self, step):
         if self.master_mode:
@@ -673,8 +727,13 @@ class FlatAdamW(torch.optim.Optimizer):
 
     def load_state_dict(self, sd):
         """the inverse of state_dict().  With skip_nonfinite the device's counters and the ledger restart from the loaded step
-        (as the applied count) and the dict's "skipped_steps" (0 if it has none); without it that key is ignored."""
+        (as the applied count) and the dict's "skipped_steps" (0 if it has none); without it that key is ignored.  With
+        stochastic_rounding the dict's seed replaces the constructor's (a dict without one leaves it); without it that key is
+        ignored."""
         self._load_state_dict(sd)
+        saved = (sd["param_groups"][0] if self.master_mode else sd).get("stochastic_rounding")
+        if self.stochastic_rounding and saved is not None:
+            self.sr_seed = _sr_seed(saved["seed"])
         skipped = int(self.param_groups[0].pop("skipped_steps", 0) if not self.master_mode
                       else sd["param_groups"][0].get("skipped_steps", 0))
         if self.skip_nonfinite:
@@ -714,6 +773,17 @@ class FlatAdamW(torch.optim.Optimizer):
         for s, m, v in zip(self.flat, sd["exp_avg"], sd["exp_avg_sq"]):
             s["m"].copy_(m)
             s["v"].copy_(v)
+
+
+def _sr_seed(seed):
+    """sr_seed as an int in [0, 2^64) (ValueError otherwise; bools and floats are not seeds)"""
+    try:
+        value = None if isinstance(seed, bool) else operator.index(seed)
+    except TypeError:
+        value = None
+    if value is None or not 0 <= value < 2 ** 64:
+        raise ValueError(f"FlatAdamW: sr_seed must be an integer in [0, 2^64) ({seed!r} given)")
+    return value
 
 
 def flat_layout(reducer):

@@ -502,6 +502,41 @@ int dvla_adamw_f32_master_grouped(float* param, const float* grad, float* exp_av
                                   const double* weight_decay, double beta1, double beta2, double eps, int64_t step,
                                   const float* grad_sumsq, float max_norm, const dvla_step_state* state, const float* ema_w,
                                   int32_t n_cand, void* stream);
+/* (additive, ABI 9) Stochastic rounding of the bf16 stores: a stored value equals its fp32 value in expectation,
+ * so updates below half a bf16 spacing land with the right frequency instead of never.
+ * The rounding, on the 32 bits u of the fp32 value and 16 random bits r (all integer arithmetic):
+ *     exponent all ones, mantissa zero (+-inf):  u >> 16
+ *     exponent all ones, mantissa not zero (NaN): (u >> 16) | 0x0040
+ *     anything else:                              (u + r) >> 16
+ *   A value that is a bf16 already (low 16 bits zero) comes back unchanged for every r; otherwise the magnitude goes up with
+ *   probability low16 / 65536 (negative values and denormals alike, -0 stays -0); a finite value above the largest bf16 may
+ *   become inf, as it does under round-to-nearest.
+ * The random bits are counter-based and stateless: a pure function of (seed: 64 bits, step: 64 bits, bucket: 32 bits,
+ * stream: 0 = param, 1 = exp_avg, 2 = exp_avg_sq, element index i: 64 bits), whatever the grid, the split of a bucket into ranges
+ * or the rank.  With hash32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 (uint32 arithmetic):
+ *     k = hash32(lo32(seed) ^ 0x243F6A88); k = hash32(k ^ hi32(seed)); k = hash32(k ^ lo32(step)); k = hash32(k ^ hi32(step));
+ *     k = hash32(k ^ bucket)                                                          -- the launch key
+ *     h = hash32((k ^ (hi32(i) * 0x85EBCA6B)) + lo32(i) * 0x9E3779B9)                 -- per element
+ *     r[0] = h >> 16,  r[1] = h & 0xffff,  r[2] = hash32(h ^ 0x5BD1E995) >> 16        -- per stream
+ *   (tests/sr_ref.py restates generator and rounding in integer arithmetic).
+ * dvla_sr_cast_f32_to_bf16: out[j] = the rounding of x[j] with r[stream] of element index index_base + j, j < n.  x and out need
+ *   no more than their elements' own alignment.  DVLA_ERR_ARG: a null pointer, n < 0, stream outside 0 .. 2.  n == 0: DVLA_OK, nothing launched.
+ * dvla_adamw_bf16_sr: dvla_adamw_bf16_grouped (its arguments, its fp32 arithmetic element for element, its guard and EMA) with
+ *   the three final conversions of param, exp_avg and exp_avg_sq rounded as above instead of to nearest; the rounding of the
+ *   clipped gradient stays round-to-nearest, and the EMA follows the parameter as stored.  group_map may be NULL: then n_groups
+ *   must be 1 and every element is stepped with (lr[0], weight_decay[0]) -- the one-group step, plain, guarded, with or without
+ *   the EMA.  Element j of the launch has index sr_index_base + j (a launch over a range of a bucket passes the range's offset:
+ *   a bucket stepped in several ranges draws the bits of one stepped whole).  The key's step is the count of APPLIED steps this
+ *   step becomes: `step` with state == NULL, state->applied (as dvla_step_verdict left it) otherwise, so a skipped step draws
+ *   nothing and does not advance the key.  Errors as dvla_adamw_bf16_grouped, + DVLA_ERR_ARG for group_map == NULL with
+ *   n_groups != 1 and for sr_index_base < 0. */
+int dvla_sr_cast_f32_to_bf16(const float* x, void* out, int64_t n, uint64_t seed, uint64_t step, int32_t bucket, int32_t stream,
+                             int64_t index_base, void* hip_stream);
+int dvla_adamw_bf16_sr(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, float* ema, int64_t n,
+                       const uint8_t* group_map, int32_t n_groups, const double* lr, const double* weight_decay, float beta1,
+                       float beta2, float eps, int64_t step, const float* grad_sumsq, float max_norm,
+                       const dvla_step_state* state, const float* ema_w, int32_t n_cand, uint64_t sr_seed, int32_t sr_bucket,
+                       int64_t sr_index_base, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Token assembly (models/dreamvla_model.py:739-759): out[b, s, t, :] = part_k[b, s, t - tok_begin_k, :] + pos[s, :]
