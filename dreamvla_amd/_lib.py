@@ -114,6 +114,7 @@ class StepState(C.Structure):
 
 STEP_READBACK_BYTES = 32
 STEP_MAX_GROUPS = 64                                 # DVLA_STEP_MAX_GROUPS
+STATS_CHUNK, STATS_PARTIAL_BYTES = 8192, 16          # DVLA_STATS_CHUNK, DVLA_STATS_PARTIAL_BYTES
 
 
 class GroupRow(C.Structure):
@@ -219,6 +220,11 @@ SYMBOLS = {
     "dvla_adamw_bf16_sr": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P, _I32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.c_float, C.c_float, C.c_float, _I64, _P, C.c_float, _P, C.POINTER(C.c_float), _I32,
                                      C.c_uint64, _I32, _I64, _P]),
+    "dvla_segment_stats_bf16": (C.c_int, [_P, _I64, _P, _I64, _P, _P]),
+    "dvla_segment_stats_f32": (C.c_int, [_P, _I64, _P, _I64, _P, _P]),
+    "dvla_segment_adam_bf16": (C.c_int, [_P, _P, _I64, _P, _I64, _P, C.c_float, C.c_float, _I64, _P]),
+    "dvla_segment_adam_f32": (C.c_int, [_P, _P, _I64, _P, _I64, _P, C.c_double, C.c_double, _I64, _P]),
+    "dvla_segment_combine": (C.c_int, [_P, _I64, _P, _I32, _P, _P, _P, _I64, _P]),
 }
 
 _lib = None

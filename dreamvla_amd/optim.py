@@ -31,6 +31,11 @@ which group's lr and weight decay a vector takes, guard and EMA included.  `weig
 Stochastic rounding (`stochastic_rounding=True`, an addition): bf16 buckets are stepped by `dvla_adamw_bf16_sr`,
 which stores parameters and both moments rounded up with a probability equal to the discarded fraction, from counter-based random
 bits (include/dvla.h); launch for launch the step of the same combination of guard, EMA and groups.
+
+Per-parameter statistics (`parameter_stats()`, `stats_by_module`, an addition): every parameter is a segment of the
+flat buffers, so `dvla_segment_stats_*` / `dvla_segment_adam_*` (one launch per bucket and buffer) and `dvla_segment_combine` (one
+launch) give per-parameter gradient and parameter norms, absmax and non-finite counts and the norm of the Adam update, with no
+atomics, no host synchronisation and no change to the step.
 """
 import collections
 import contextlib
@@ -587,6 +592,105 @@ class FlatAdamW(torch.optim.Optimizer):
         """total gradient norm of the last step() with clipping (device scalar tensor)"""
         return self._sumsq.sqrt()
 
+    # ---- per-parameter statistics (parameter_stats) ----------------------------------------------------------------------------
+    def _stats_tables(self):
+        """the chunk table of every bucket (device tensor, number of chunks, index of its first record), the segment table of all
+        buckets together and the scratch of one record per chunk: built and uploaded on first use"""
+        if getattr(self, "_stats_cache", None) is None:
+            index = {id(p): i for i, p in enumerate(self.reducer.params)}
+            dev = self.reducer.buckets[0]["flat"].device
+            tabs, all_segs, first = [], [], 0
+            for b in self.reducer.buckets:
+                chunks, segs = build_chunk_table(b["offsets"], [p.numel() for p in b["params"]], b["flat"].numel(),
+                                                 [index[id(p)] for p in b["params"]], first_record=first)
+                pad = torch.zeros(1, 2, dtype=torch.int64)          # (an empty table still has an address)
+                tabs.append((torch.cat([chunks, pad]).to(dev), chunks.shape[0], first))
+                all_segs.append(segs)
+                first += chunks.shape[0]
+            segs = torch.cat(all_segs + [torch.zeros(1, 3, dtype=torch.int64)]).to(dev)
+            scratch = torch.empty(max(first, 1) * _lib.STATS_PARTIAL_BYTES, dtype=torch.uint8, device=dev)
+            self._stats_cache = (tabs, first, segs, scratch)
+        return self._stats_cache
+
+    def _group_masks(self):
+        """per parameter group: 1.0 at its parameters' positions in reducer.params (device fp32, built once: the groups are fixed)"""
+        if getattr(self, "_stats_masks", None) is None:
+            dev = self.reducer.buckets[0]["flat"].device
+            which = torch.tensor([self._group_of[id(p)] for p in self.reducer.params], dtype=torch.int64)
+            self._stats_masks = [(which == gi).to(torch.float32).to(dev) for gi in range(len(self.param_groups))]
+        return self._stats_masks
+
+    @torch.no_grad()
+    def parameter_stats(self, what=("grad", "param", "update")):
+        """Per-parameter reductions over the flat buffers -> dict of 1-D device tensors of length len(reducer.params), in
+        reducer.params order, computed by segmented reductions on the current stream (one launch per bucket and buffer and one
+        more per buffer, no atomics, no host synchronisation but the one named below); the step is not touched and a run that never calls this
+        issues the launches it always did.  `what` selects:
+          "grad"    grad_norm, grad_absmax (largest |g| over the elements that are not NaN; inf if there is an inf),
+                    grad_nonfinite (int64: the number of NaN / inf elements) of the gradient buckets as they stand.  The step
+                    kernels do not write the gradient, so after reducer.finish() -- before or after step() -- this is the
+                    reduced, UNCLIPPED gradient; after a skipped step grad_nonfinite.nonzero() names the parameter(s) that
+                    made it skip, until zero_grad().
+          "param"   param_norm, param_absmax, param_nonfinite of the parameters (the fp32 masters in master mode)
+          "update"  update_norm = lr_g |1 / (1 - beta1^t)| sqrt(sum r^2), r = exp_avg / denom(exp_avg_sq) with the step's own
+                    denominator, t the current step count and lr_g the lr of the parameter's group read afresh from param_groups.
+                    On fp32 masters this is the norm of the Adam term the LAST step added to the parameter, element for
+                    element, before weight decay.  On bf16 buckets it is the same term recomputed from the moments AS STORED
+                    (rounded to bf16, or stochastically rounded), not the fp32 values the step held in registers.  0 before the
+                    first step and for parameters the step leaves alone (their moments stay zero).  With skip_nonfinite t is
+                    `applied_steps`, so the call waits for every enqueued step exactly as that property does.
+        A parameter's numbers depend on its own elements only -- not on the bucket it sits in or on bucket_bytes -- and two
+        calls give the same bits; the relative error of a norm is below (STATS_CHUNK / 256 + 10) 2^-24.
+        Alignment gaps are never read.  Raises RuntimeError inside ema_weights() (the buffers hold the EMA) and ValueError for an
+        unknown entry of `what`.  Tables and scratch are allocated on first use.  stats_by_module() sums over modules."""
+        what = (what,) if isinstance(what, str) else tuple(what)
+        for w in what:
+            if w not in STATS_KEYS:
+                raise ValueError(f"FlatAdamW.parameter_stats: unknown entry {w!r} of `what` (known: {', '.join(STATS_KEYS)})")
+        if self._ema_active:
+            raise RuntimeError("FlatAdamW.parameter_stats() inside ema_weights(): the flat buffers hold the EMA weights")
+        lib = _lib.load()
+        stream = torch.cuda.current_stream().cuda_stream
+        tabs, n_records, segs, scratch = self._stats_tables()
+        n = len(self.reducer.params)
+        dev = scratch.device
+        out = {}
+
+        def stage1(fn, s, keys, chunks, n_chunks, first, *more):
+            if n_chunks:        # (a bucket of empty parameters has no buffer to speak of)
+                check(fn(*[s[k].data_ptr() for k in keys], s[keys[0]].numel(), chunks.data_ptr(), n_chunks,
+                         scratch.data_ptr() + first * _lib.STATS_PARTIAL_BYTES, *more, stream), "dvla_segment_*")
+
+        for w, key in (("grad", "g"), ("param", "p")):
+            if w not in what:
+                continue
+            sumsq, absmax = torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.float32, device=dev)
+            bad = torch.zeros(n, dtype=torch.int64, device=dev)
+            for s, tab in zip(self.flat, tabs):
+                stage1(lib.dvla_segment_stats_f32 if s[key].dtype == torch.float32 else lib.dvla_segment_stats_bf16, s, (key,), *tab)
+            check(lib.dvla_segment_combine(scratch.data_ptr(), n_records, segs.data_ptr(), n, sumsq.data_ptr(), absmax.data_ptr(),
+                                           bad.data_ptr(), n, stream), "dvla_segment_combine")
+            out[w + "_norm"], out[w + "_absmax"], out[w + "_nonfinite"] = sumsq.sqrt_(), absmax, bad
+        if "update" in what:
+            t = self.applied_steps if self.skip_nonfinite else self.step_count
+            sumsq = torch.zeros(n, dtype=torch.float32, device=dev)
+            if t > 0:
+                b1, b2, eps = common_betas_eps(self.param_groups)
+                for s, tab in zip(self.flat, tabs):
+                    stage1(lib.dvla_segment_adam_f32 if "sh" in s else lib.dvla_segment_adam_bf16, s, ("m", "v"), *tab, b2, eps, t)
+                check(lib.dvla_segment_combine(scratch.data_ptr(), n_records, segs.data_ptr(), n, sumsq.data_ptr(), None, None, n,
+                                               stream), "dvla_segment_combine")
+                bc1 = abs(1.0 / (1.0 - b1 ** t))
+                if len(self.param_groups) == 1:
+                    scale = float(self.param_groups[0]["lr"]) * bc1
+                else:       # Python scalars times cached device masks: no upload
+                    scale = torch.zeros(n, dtype=torch.float32, device=dev)
+                    for g, mask in zip(self.param_groups, self._group_masks()):
+                        scale.add_(mask, alpha=float(g["lr"]) * bc1)
+                sumsq = sumsq.sqrt_().mul_(scale)
+            out["update_norm"] = sumsq
+        return out
+
     def _layout(self):
         return flat_layout(self.reducer)
 
@@ -853,6 +957,69 @@ def build_group_map(offsets, sizes, total, group_ids, stepped, n_groups):
         if used and n > 0:
             out[off // 8:(off + n + 7) // 8] = gid
     return out
+
+
+def build_chunk_table(offsets, sizes, total, out_index=None, chunk=_lib.STATS_CHUNK, first_record=0):
+    """the chunk table of one bucket for the segmented reductions (include/dvla.h; pure) -> (chunks, segs), CPU int64 tensors.
+    Parameter j occupies elements offsets[j] .. offsets[j] + sizes[j] of its bucket and is cut into chunks of `chunk` elements
+    counted from ITS OWN first element (the last one shorter), so the cuts -- and with them the order in which a parameter's
+    elements are added -- do not depend on where the parameter sits or on what else the bucket holds.  chunks[c] = (element
+    offset in the bucket, length), a parameter's chunks in consecutive rows; segs[j] = (first_record + its first chunk, number of
+    chunks -- 0 for an empty parameter --, out_index[j], by default j): the buckets of an optimizer share one scratch of records.  Every parameter is in the table, stepped or not; alignment gaps are in no
+    chunk.  Parameters start on multiples of 8 elements and `chunk` is a multiple of 8, so every chunk does."""
+    if chunk <= 0 or chunk % 8:
+        raise ValueError(f"FlatAdamW: the chunk length {chunk} is not a positive multiple of 8")
+    out_index = list(range(len(sizes))) if out_index is None else list(out_index)
+    chunks, segs = [], []
+    for off, n, o in zip(offsets, sizes, out_index):
+        off, n = int(off), int(n)
+        if off % 8:
+            raise ValueError(f"FlatAdamW: a parameter starts at element {off} of its bucket, not on a multiple of 8")
+        if off < 0 or n < 0 or off + n > total:
+            raise ValueError(f"FlatAdamW: a parameter ends at element {off + n} of a bucket of {total}")
+        segs.append((int(first_record) + len(chunks), -(-n // chunk), int(o)))
+        chunks.extend((off + lo, min(chunk, n - lo)) for lo in range(0, n, chunk))
+    return (torch.tensor(chunks, dtype=torch.int64).reshape(-1, 2), torch.tensor(segs, dtype=torch.int64).reshape(-1, 3))
+
+
+STATS_KEYS = {"grad": ("grad_norm", "grad_absmax", "grad_nonfinite"), "param": ("param_norm", "param_absmax", "param_nonfinite"),
+              "update": ("update_norm",)}
+
+
+def stats_by_module(stats, model_or_named_parameters, reducer, depth=2):
+    """FlatAdamW.parameter_stats() per module -> (names, dict of tensors of length len(names)).  The parameters of `reducer.params`
+    are matched by identity with the model's named parameters (as ema_model_state_dict does; a shared parameter counts once, under
+    its first name) and a name is cut to its first `depth` dotted components: "trunk.h.3.attn.c_attn.weight" is "trunk.h" at
+    depth 2.  Parameters of the reducer the model does not name go under "<unnamed>".  `*_norm` entries combine as the root of
+    the sum of squares, `*_absmax` as the maximum, `*_nonfinite` as the sum.  names are in order of first appearance in
+    reducer.params.  Pure torch on tiny tensors (a few launches on the tensors' device; CPU tensors work)."""
+    named = model_or_named_parameters
+    named = named.named_parameters(remove_duplicate=False) if hasattr(named, "named_parameters") else named
+    name_of = {}
+    for name, p in named:
+        name_of.setdefault(id(p), name)
+    names, owner = [], []
+    for p in reducer.params:
+        full = name_of.get(id(p))
+        key = "<unnamed>" if full is None else ".".join(full.split(".")[:max(1, int(depth))])
+        if key not in names:
+            names.append(key)
+        owner.append(names.index(key))
+    out = {}
+    for key, t in stats.items():
+        if t.shape != (len(owner),):
+            raise ValueError(f"stats_by_module: {key!r} has shape {tuple(t.shape)}, the reducer {len(owner)} parameters")
+        idx = torch.tensor(owner, dtype=torch.int64).to(t.device)
+        if key.endswith("_norm"):
+            acc = torch.zeros(len(names), dtype=torch.float64, device=t.device)
+            out[key] = acc.index_add_(0, idx, t.double() ** 2).sqrt().to(t.dtype)
+        elif key.endswith("_absmax"):
+            out[key] = torch.zeros(len(names), dtype=t.dtype, device=t.device).scatter_reduce_(0, idx, t, "amax", include_self=True)
+        elif key.endswith("_nonfinite"):
+            out[key] = torch.zeros(len(names), dtype=t.dtype, device=t.device).index_add_(0, idx, t)
+        else:
+            raise ValueError(f"stats_by_module: do not know how to combine {key!r} (expected *_norm, *_absmax or *_nonfinite)")
+    return names, out
 
 
 def weight_decay_groups(module_or_named_parameters, weight_decay, skip=()):

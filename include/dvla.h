@@ -537,6 +537,46 @@ int dvla_adamw_bf16_sr(void* param, const void* grad, void* exp_avg, void* exp_a
                        float beta2, float eps, int64_t step, const float* grad_sumsq, float max_norm,
                        const dvla_step_state* state, const float* ema_w, int32_t n_cand, uint64_t sr_seed, int32_t sr_bucket,
                        int64_t sr_index_base, void* stream);
+/* (additive, ABI 9) Per-parameter reductions over the flat optimizer buffers: every parameter of a bucket is a
+ * segment of the gradient, parameter and moment buffers at the same element offsets.  Stage 1 (one launch per bucket and buffer)
+ * reduces chunks of segments into records, stage 2 (dvla_segment_combine: one launch for all buckets) adds every segment's
+ * records: no atomics, no host synchronisation, nothing the step kernels do changes.
+ * The chunk table (host-built; dreamvla_amd/optim.py: build_chunk_table): every segment is cut into chunks of DVLA_STATS_CHUNK
+ *   elements counted from the segment's OWN first element, the last one shorter; segments start on multiples of 8 elements.
+ *     chunks[2 c], chunks[2 c + 1]   element offset in the buffer and length (<= DVLA_STATS_CHUNK) of chunk c of a bucket; the
+ *                                    chunks of a segment are consecutive rows, in order
+ *     segs[3 j .. 3 j + 2]           first record, number of records (0 for an empty segment) and output index of segment j
+ *   Both live in device memory.  partial: device scratch of DVLA_STATS_PARTIAL_BYTES per chunk; stage 1 writes record c of its
+ *   bucket at partial + c * DVLA_STATS_PARTIAL_BYTES, so the buckets of one optimizer pass consecutive regions of one scratch
+ *   and segs counts records from its start.  A row that does not lie inside the buffer (n elements), the records (n_chunks)
+ *   or the outputs (n_out) is not followed: nothing is read or written for it (a chunk row: a record of zeros).
+ *   A segment's results depend on its own elements and on nothing else -- not on the grid, the other segments, the bucket or the
+ *   segment's offset -- and two calls give the same bits.  Elements outside every chunk (alignment gaps) are never read.
+ * dvla_segment_stats_bf16 / _f32: per chunk the sum of x^2, the largest |x| over the elements that are not NaN and the number of
+ *   NaN / +-inf elements.  dvla_segment_adam_bf16 / _f32: per chunk the sum of r^2, r = exp_avg / denom(exp_avg_sq) with the step
+ *   kernels' own expressions,
+ *     fp32 masters:  denom = rn(rn(rn(sqrt(v)) / bc2_sqrt) + eps), r = rn(m / denom)          (dvla_adamw_f32_master)
+ *     bf16:          denom = fma(sqrt(v), inv_bc2_sqrt, eps),       r = m / denom, on the stored moments widened to fp32
+ *   and bc2_sqrt / inv_bc2_sqrt those of dvla_step_candidates for `step` (the count of the step that wrote the moments).  No lr
+ *   enters: lr / (1 - beta1^step) * sqrt(sum r^2) is the norm of the Adam term that step added to the parameter.
+ * dvla_segment_combine: for segment j, at output index o = segs[3 j + 2], its records added in order (the sum in double),
+ *     sumsq[o]      the sum, fp32 (error bound: DESIGN.md 4.3); NaN / inf if the segment holds one
+ *     absmax[o]     max |x| over the elements that are not NaN (fmaxf; an inf gives inf); 0 for an empty or all-NaN segment
+ *     nonfinite[o]  the number of NaN and +-inf elements, exact
+ *   absmax and nonfinite may be NULL (the Adam term has neither).
+ * DVLA_ERR_ARG: a null pointer, a negative count, step < 1.  n_chunks == 0 (stage 1) or n_segs == 0 (stage 2): DVLA_OK, nothing
+ * launched.  DVLA_ERR_UNSUPPORTED: a buffer, chunk table or scratch base that is not 16-byte aligned.  All of these return
+ * before anything touches the device. */
+#define DVLA_STATS_CHUNK 8192
+#define DVLA_STATS_PARTIAL_BYTES 16
+int dvla_segment_stats_bf16(const void* x, int64_t n, const int64_t* chunks, int64_t n_chunks, void* partial, void* stream);
+int dvla_segment_stats_f32(const float* x, int64_t n, const int64_t* chunks, int64_t n_chunks, void* partial, void* stream);
+int dvla_segment_adam_bf16(const void* exp_avg, const void* exp_avg_sq, int64_t n, const int64_t* chunks, int64_t n_chunks,
+                           void* partial, float beta2, float eps, int64_t step, void* stream);
+int dvla_segment_adam_f32(const float* exp_avg, const float* exp_avg_sq, int64_t n, const int64_t* chunks, int64_t n_chunks,
+                          void* partial, double beta2, double eps, int64_t step, void* stream);
+int dvla_segment_combine(const void* partial, int64_t n_chunks, const int64_t* segs, int32_t n_segs, float* sumsq, float* absmax,
+                         int64_t* nonfinite, int64_t n_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Token assembly (models/dreamvla_model.py:739-759): out[b, s, t, :] = part_k[b, s, t - tok_begin_k, :] + pos[s, :]
