@@ -97,6 +97,7 @@ class MaeLossParams(C.Structure):
                 ("mask", C.c_void_p), ("N", C.c_int64)]
 
 
+PROBE_MAX_ROWS = 32                                  # DVLA_PROBE_MAX_ROWS
 STEP_MAX_BUCKETS, STEP_MAX_CANDIDATES = 256, 9      # DVLA_STEP_MAX_* of include/dvla.h
 
 
@@ -142,6 +143,7 @@ SYMBOLS = {
     "dvla_attn_small_bwd": (C.c_int, [C.POINTER(AttnParams), _I32, _P]),
     "dvla_attn_hd_fwd": (C.c_int, [C.POINTER(AttnParams), _I32, _P]),
     "dvla_attn_hd_bwd": (C.c_int, [C.POINTER(AttnParams), _I32, _P]),
+    "dvla_attn_probe": (C.c_int, [C.POINTER(AttnParams), _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "dvla_colsum_dt": (C.c_int, [_P, _I64, _I64, _I64, _P, _I32, _P, _P]),
     "dvla_colsum_partial_rows": (_I64, []),
     "dvla_dropout": (C.c_int, [_P, _P, _I64, _I64, _F, _U32, _U32, _P]),

@@ -417,6 +417,81 @@ class DreamVLA(nn.Module):
                           self.traj_decoder, self.traj_decoder_norm, self.traj_decoder_pred, "none"))
         return heads
 
+    def token_groups(self):
+        """[(name, start, count)] of the token groups of one frame block of the trunk's sequence, in token order, from the model's
+        own counters: text, state, image_primary, image_wrist, cls_primary, cls_wrist, one group per dream-query family
+        ("dream_image", "dream_depth", "dream_dino", "dream_sam", "dream_traj"; with share_query every head reads its columns of
+        the SAME rows -- `_dream_heads` -- so there is one group, "dream_shared"), action.  The groups tile the block."""
+        nq = self.NUM_RESAMPLER_QUERY
+        groups = [("text", 1), ("state", 1), ("image_primary", nq), ("image_wrist", nq), ("cls_primary", 1), ("cls_wrist", 1)]
+        if self.share_query:
+            if self.NUM_OBS_TOKEN:
+                groups.append(("dream_shared", self.NUM_OBS_TOKEN))
+        else:
+            for name, count in (("image", self.NUM_OBS_TOKEN), ("depth", self.NUM_DEPTH_TOKEN), ("dino", self.NUM_DINO_TOKEN),
+                                ("sam", self.NUM_SAM_TOKEN), ("traj", self.NUM_TRAJ_TOKEN)):
+                if count:
+                    groups.append(("dream_" + name, count))
+        if self.action_pred_steps > 0:
+            groups.append(("action", self.action_pred_steps))
+        out, cur = [], 0
+        for name, count in groups:
+            out.append((name, cur, count))
+            cur += count
+        return out
+
+    def _attention_probe(self, attention, B, S, test_select, device):
+        """the ops.AttentionProbe of an `attention` spec of decode_tokens: dict(rows="action" | "obs" | (B, R) int tensor,
+        layers="all" | "last" | sequence of ints).  The row numbers are computed on the device from `test_select` (no host read)."""
+        if not isinstance(attention, dict) or set(attention) - {"rows", "layers"}:
+            raise ValueError('attention: None or dict(rows="action" | "obs" | (B, R) int tensor, layers="all" | "last" | ints)')
+        rows, layers = attention.get("rows", "action"), attention.get("layers", "all")
+        n_layer = len(self.transformer_backbone.h)
+        if isinstance(layers, str):
+            if layers not in ("all", "last"):
+                raise ValueError('attention["layers"]: "all", "last" or a sequence of layer indices')
+            layers = None if layers == "all" else (n_layer - 1,)
+        else:
+            layers = tuple(int(i) for i in layers)
+            if not layers or any(not 0 <= i < n_layer for i in layers) or list(layers) != sorted(set(layers)):
+                raise ValueError(f'attention["layers"]: ascending indices out of 0..{n_layer - 1}')
+        sel_rows = DreamVLA._attention_rows(self, rows, B, S, test_select, device)
+        return ops.AttentionProbe(sel_rows, layers)
+
+    def _attention_rows(self, rows, B, S, select, device):
+        """(B, R) int32 trunk rows on the device for rows = "action" | "obs" | an int (B, R) tensor; `select` (B,) = the window
+        position whose queries are meant (a device tensor: the arithmetic stays on the device), None = every position"""
+        if torch.is_tensor(rows):
+            if rows.dim() != 2 or rows.shape[0] != B or rows.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f'attention["rows"]: an int ({B}, R) tensor of trunk rows')
+            sel_rows = rows.to(device=device, dtype=torch.int32)
+        else:
+            by_name = {name: (start, count) for name, start, count in DreamVLA.token_groups(self)}
+            blk = sum(count for _, count in by_name.values())
+            if rows == "action":
+                if "action" not in by_name:
+                    raise ValueError('attention["rows"] = "action": this model has no action queries')
+                start, count = by_name["action"]
+            elif rows == "obs":
+                dream = [v for k, v in by_name.items() if k.startswith("dream_")]
+                if not dream:
+                    raise ValueError('attention["rows"] = "obs": this model has no dream queries')
+                start, count = dream[0][0], sum(c for _, c in dream)
+            else:
+                raise ValueError('attention["rows"]: "action", "obs" or an int (B, R) tensor')
+            inner = torch.arange(start, start + count, dtype=torch.int32, device=device)
+            if select is not None:
+                if tuple(select.shape) != (B,):
+                    raise ValueError(f"test_select {tuple(select.shape)}: expected ({B},)")
+                sel_rows = select.to(device=device, dtype=torch.int32).view(B, 1) * blk + inner.view(1, -1)
+            else:
+                pos = torch.arange(S, dtype=torch.int32, device=device) * blk
+                sel_rows = (pos.view(S, 1) + inner.view(1, -1)).reshape(1, -1).expand(B, -1)
+        if not 1 <= sel_rows.shape[1] <= ops.PROBE_MAX_ROWS:
+            raise ValueError(f'attention: {sel_rows.shape[1]} rows per sequence; the probe takes 1 to {ops.PROBE_MAX_ROWS} '
+                             f'(pass test_select, or name the rows)')
+        return sel_rows.contiguous()
+
     def _dream_head(self, feat, n2, n_q, n_mask, projector, mask_token, pos, decoder, norm, pred, act="none"):
         """feat: (B, S, n_tok, Hin) slice of the trunk output -> pred (n2*n_mask, out).  dreamvla_model.py:793-911."""
         Hd = self.hidden_dim
@@ -473,12 +548,15 @@ class DreamVLA(nn.Module):
             text_feature = self.clip_model.encode_text(text_token.flatten(0, 1))
         return self.text_projector(text_feature.to(torch.bfloat16)).view(B, S, -1, self.hidden_dim)
 
-    def encode_frames(self, image_primary, image_wrist, state, text_token, text_embedding=None):
+    def encode_frames(self, image_primary, image_wrist, state, text_token, text_embedding=None, attention=None):
         """Conditioning tokens of every frame, as the list [text (B,S,1,H), state (B,S,1,H), primary image (B,S,nq,H),
         wrist image (B,S,nq,H), cls primary (B,S,1,H), cls wrist (B,S,1,H)]  (dreamvla_model.py:643-737).  Each frame
         is encoded independently of every other frame and of its position in the window (the window position embedding
         is added in `decode_tokens`), which is what lets dreamvla_amd.rollout.RolloutEngine keep the tokens of the
-        frames it has already seen and encode only the newest one per control step."""
+        frames it has already seen and encode only the newest one per control step.
+        `attention` (an addition; eval() only): anything but None leaves the resampler's attention maps of the encoded frames in
+        `self.last_attention["resampler"]`, fp32 (2 * B * S, depth, nq, 196 + nq): the primary views of all frames, then the
+        wrist views; every latent row of every layer, head mean, columns = patches then latents.  The tokens do not depend on it."""
         B, S, _ = state.shape
         H = self.hidden_dim
         wdt = torch.bfloat16     # compute dtype: fp32 parameters are masters, the kernels run on bf16 shadows (ops.shadow)
@@ -515,7 +593,12 @@ class DreamVLA(nn.Module):
         # strided view (6 x 49 us per step in the torch profile; round 6)
         patches = feats[:, 1:, :].contiguous()
         # perceiver resampler (shared weights, both views batched)                        (716-717)
-        lat = self.perceiver_resampler(patches.unsqueeze(1).unsqueeze(1))                 # (2n, 1, nq, 768)
+        if attention is None:
+            lat = self.perceiver_resampler(patches.unsqueeze(1).unsqueeze(1))             # (2n, 1, nq, 768)
+        else:
+            probe = ops.AttentionProbe()
+            lat = self.perceiver_resampler(patches.unsqueeze(1).unsqueeze(1), probe=probe)
+            self.last_attention = dict(getattr(self, "last_attention", None) or {}, resampler=probe.maps)
         nq = lat.shape[-2]
         lat = lat.reshape(2, n * nq, self.RESAMPLER_hidden_dim)
         image_primary_embedding = self.image_primary_projector(lat[0]).view(B, S, -1, H)
@@ -541,7 +624,7 @@ class DreamVLA(nn.Module):
 
         return [text_embedding, state_embedding, image_primary_embedding, image_wrist_embedding, cls_primary, cls_wrist]
 
-    def decode_tokens(self, parts, action_label=None, mode='train', test_noise=None, test_select=None, dreams=None):
+    def decode_tokens(self, parts, action_label=None, mode='train', test_noise=None, test_select=None, dreams=None, attention=None):
         """Token assembly with the prediction queries, trunk, dream heads (train) and action head
         (dreamvla_model.py:739-991).  `parts`: the list from `encode_frames`, or one (B, S, 36, H) tensor of them.
         `test_noise` (B*S, action_pred_steps, 7), mode='test' with the DiT head only: the sampler's start noise as an INPUT
@@ -555,8 +638,15 @@ class DreamVLA(nn.Module):
         {"image", "depth", "dino", "sam", "traj"} -- the matching slots of the returned tuple then carry that head's prediction
         instead of None, computed under no_grad on the kernels of the training path: every window position, shaped as in train
         mode (B*S, views, pred_num, rows, cols), or with `test_select` (any action head) the selected position only, (B, views,
-        ...).  A head the model was not built with raises ValueError.  The action outputs do not depend on `dreams`."""
+        ...).  A head the model was not built with raises ValueError.  The action outputs do not depend on `dreams`.
+        `attention`, mode='test' only (an addition): None, or dict(rows=..., layers=...) -- where the trunk's attention goes.
+        rows: "action" = the action queries of the position in `test_select` (of every position without it: S * steps rows,
+        at most ops.PROBE_MAX_ROWS), "obs" = the dream queries likewise, or an int (B, R) tensor of trunk rows; layers: "all",
+        "last" or ascending indices.  `self.last_attention["trunk"]` is then fp32 (B, n_layers, R, L): the head-mean softmax
+        probabilities of those rows under the trunk's mask (ops.attention_probe).  The returned tuple does not depend on it."""
         want = self._check_dreams(dreams) if mode != 'train' else ()
+        if attention is not None and mode != 'test':
+            raise ValueError("attention maps are an evaluation instrument: mode='test' only")
         if torch.is_tensor(parts):
             parts = [parts]
         else:
@@ -591,8 +681,14 @@ class DreamVLA(nn.Module):
 
         # trunk                                                                              (762-790)
         transformer_input = self.embedding_layer_norm(transformer_input)
-        transformer_output = self.transformer_backbone(inputs_embeds=transformer_input, attention_mask=self.attention_mask,
-                                                       mask_tables=getattr(self, "_step_mask_tables", None))
+        if attention is None:
+            transformer_output = self.transformer_backbone(inputs_embeds=transformer_input, attention_mask=self.attention_mask,
+                                                           mask_tables=getattr(self, "_step_mask_tables", None))
+        else:
+            probe = self._attention_probe(attention, B, S, test_select, transformer_input.device)
+            transformer_output = self.transformer_backbone(inputs_embeds=transformer_input, attention_mask=self.attention_mask,
+                                                           mask_tables=getattr(self, "_step_mask_tables", None), probe=probe)
+            self.last_attention = dict(getattr(self, "last_attention", None) or {}, trunk=probe.maps)
         transformer_output = transformer_output.view(B, S, -1, H)
 
         # dream heads: training -- and, for the heads named in `dreams`, evaluation                  (792-911)

@@ -56,9 +56,12 @@ class GPT2Attention(nn.Module):
         self.c_proj = Conv1D(self.embed_dim, self.embed_dim)
         self.attn_pdrop, self.resid_pdrop = config.attn_pdrop, config.resid_pdrop
 
-    def forward(self, hidden_states, mask_tables=None, residual=None):
+    def forward(self, hidden_states, mask_tables=None, residual=None, probe=None):
         qkv = self.c_attn(hidden_states)
-        o = ops.self_attention(qkv, self.num_heads, scale=1.0 / math.sqrt(self.head_dim), mask_tables=mask_tables,
+        scale = 1.0 / math.sqrt(self.head_dim)
+        if probe is not None:      # evaluation instrument (ops.AttentionProbe): reads the qkv the attention below reads
+            probe.record_packed(qkv, self.num_heads, self.head_dim, scale=scale, mask_tables=mask_tables)
+        o = ops.self_attention(qkv, self.num_heads, scale=scale, mask_tables=mask_tables,
                                dropout_p=self.attn_pdrop if self.training else 0.0, head_dim=self.head_dim)
         return self.c_proj(o, residual=residual, dropout_p=self.resid_pdrop if self.training else 0.0)
 
@@ -90,9 +93,9 @@ class GPT2Block(nn.Module):
         self.ln_2 = LayerNorm(hidden_size, eps=config.layer_norm_epsilon)
         self.mlp = GPT2MLP(inner_dim, config)
 
-    def forward(self, hidden_states, mask_tables=None):
+    def forward(self, hidden_states, mask_tables=None, probe=None):
         res, normed = self.ln_1.fork(hidden_states)     # x and LN(x): backward adds dL/dx of both paths in one kernel
-        hidden_states = self.attn(normed, mask_tables=mask_tables, residual=res)
+        hidden_states = self.attn(normed, mask_tables=mask_tables, residual=res, probe=probe)
         res, normed = self.ln_2.fork(hidden_states)
         return self.mlp(normed, residual=res)
 
@@ -122,9 +125,13 @@ class GPT2Model(nn.Module):
             if name == "c_proj.weight":
                 p.data.normal_(mean=0.0, std=(std / math.sqrt(2 * self.config.n_layer)))
 
-    def forward(self, attention_mask=None, inputs_embeds=None, mask_tables=None):
+    def forward(self, attention_mask=None, inputs_embeds=None, mask_tables=None, probe=None):
         """inputs_embeds (B, L, H); attention_mask: additive 0/-inf mask, (L, L) or the (B,1,L,L) expansion the
-        reference's sdpa branch builds (dreamvla_model.py:769-775) -- the batch copies are identical, row 0 is used."""
+        reference's sdpa branch builds (dreamvla_model.py:769-775) -- the batch copies are identical, row 0 is used.
+        `probe` (an addition; eval() only): an ops.AttentionProbe -- the blocks in its `layers` report the attention of its `rows`
+        under the same mask tables, `probe.maps` (B, n_layers, R, L) afterwards.  The output does not depend on it."""
+        if probe is not None:
+            probe.begin(self)
         mt = mask_tables      # tables built on the device from the mask rule (pretrain phase): `attention_mask` is then unused
         if mt is None and attention_mask is not None:
             m2 = attention_mask
@@ -132,7 +139,12 @@ class GPT2Model(nn.Module):
                 m2 = m2[0]
             mt = ops.mask_tables_for(m2)
         hidden_states = ops.dropout(inputs_embeds, self.embd_pdrop, self.training)
-        for block in self.h:
-            hidden_states = block(hidden_states, mask_tables=mt)
+        if probe is None:
+            for block in self.h:
+                hidden_states = block(hidden_states, mask_tables=mt)
+        else:
+            for i, block in enumerate(self.h):
+                hidden_states = block(hidden_states, mask_tables=mt, probe=probe if probe.wants(i) else None)
+            probe.end()
         hidden_states = self.ln_f(hidden_states)
         return hidden_states.view(inputs_embeds.shape)

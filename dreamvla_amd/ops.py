@@ -956,6 +956,214 @@ def attn_bwd_raw(q, k, v, o, lse, dout, dq, dk, dv, *, scale, mask_tables=None, 
 
 
 # ---------------------------------------------------------------------------------------------------
+# attention probe (an addition: the reference has no such instrument)
+# ---------------------------------------------------------------------------------------------------
+PROBE_MAX_ROWS = _lib.PROBE_MAX_ROWS
+
+
+def attention_probe(q, k, rows, *, scale, mask_tables=None, per_head=False, out=None):
+    """The softmax probabilities the attention kernels apply to a few query rows (csrc/attention_probe.hip), read-only.
+    q (B, Lq, H, D), k (B, Lk, H, D): strided bf16 views with unit inner stride (the thirds of a packed qkv, the k half of the
+    resampler's kv).  rows (B, R) int32 on the device, 1 <= R <= PROBE_MAX_ROWS: the query rows of each sequence; an entry
+    outside [0, Lq) gives a zero row.  -> fp32 (B, R, Lk), the mean over heads, or (B, H, R, Lk) with per_head.  Columns are
+    key numbers of `k` as it lies in memory, whatever order or compaction `mask_tables` uses; a key the row cannot see, and a
+    row that sees nothing, hold exactly 0.  `out`: a contiguous fp32 tensor of the result's shape to write into (every element is
+    written).  No gradient.  Every argument is checked before the library is reached."""
+    for name, t in (("q", q), ("k", k)):
+        if not isinstance(t, torch.Tensor) or t.dtype != BF16 or t.dim() != 4:
+            raise ValueError(f"attention_probe: {name} must be a bf16 (B, L, H, D) tensor")
+        if t.stride(3) != 1:
+            raise ValueError(f"attention_probe: {name} needs unit inner stride")
+    B, Lq, H, D = q.shape
+    if k.shape[0] != B or k.shape[2] != H or k.shape[3] != D:
+        raise ValueError(f"attention_probe: q is {tuple(q.shape)}, k is {tuple(k.shape)}: batch, heads and head_dim must agree")
+    Lk_full = k.shape[1]
+    if B < 1 or H < 1 or Lq < 1 or Lk_full < 1:
+        raise ValueError("attention_probe: empty q or k")
+    if D % 8 != 0 or not 8 <= D <= 128:
+        raise ValueError(f"attention_probe: head_dim {D}: a multiple of 8 from 8 to 128 is supported")
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[0] != B:
+        raise ValueError(f"attention_probe: rows must be an int32 ({B}, R) tensor")
+    R = rows.shape[1]
+    if not 1 <= R <= PROBE_MAX_ROWS:
+        raise ValueError(f"attention_probe: {R} rows per sequence; 1 to {PROBE_MAX_ROWS} are supported")
+    mt = mask_tables
+    if mt is not None:
+        if not isinstance(mt, MaskTables):
+            raise ValueError("attention_probe: mask_tables must be a MaskTables")
+        if mt.Lq != Lq or mt.Lk_full != Lk_full:
+            raise ValueError(f"attention_probe: the mask is {mt.Lq}x{mt.Lk_full}, the tensors are {Lq}x{Lk_full}")
+        if not 1 <= mt.Lk <= Lk_full or (mt.key_index is None and mt.Lk != Lk_full):
+            raise ValueError("attention_probe: inconsistent mask tables (Lk against key_index / Lk_full)")
+    shape = (B, H, R, Lk_full) if per_head else (B, R, Lk_full)
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != shape
+                            or not out.is_contiguous()):
+        raise ValueError(f"attention_probe: out must be a contiguous fp32 tensor of shape {shape}")
+    for name, t in (("q", q), ("k", k), ("rows", rows)) + ((("out", out),) if out is not None else ()):
+        if not t.is_cuda or t.device != q.device:
+            raise ValueError(f"attention_probe: {name} is on {t.device}; the probe runs on the GPU, all operands on one device")
+    lib = _lib.load()
+    rows = rows.contiguous()
+    p = AttnParams()
+    p.q, p.k = q.data_ptr(), k.data_ptr()
+    for name, t in (("q", q), ("k", k)):
+        setattr(p, name + "_stride_b", t.stride(0))
+        setattr(p, name + "_stride_t", t.stride(1))
+        setattr(p, name + "_stride_h", t.stride(2))
+    p.B, p.H, p.Lq, p.Lk = B, H, Lq, Lk_full
+    p.scale = float(scale)
+    if mt is not None:
+        p.Lk = mt.Lk
+        p.key_index = _ptr(mt.key_index)
+        p.mask_bits_q = mt.bits_q.data_ptr()
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=q.device)
+    ws = None if per_head else torch.empty((B, H, R, Lk_full), dtype=torch.float32, device=q.device)
+    check(lib.dvla_attn_probe(C.byref(p), rows.data_ptr(), R, D, Lk_full, int(bool(per_head)), out.data_ptr(), _ptr(ws), _stream()),
+          "dvla_attn_probe")
+    return out
+
+
+def self_attention_probe(qkv, num_heads, rows, *, scale=None, mask_tables=None, per_head=False, head_dim=64):
+    """attention_probe on a packed qkv (B, L, 3 * H * D) -- the buffer ops.self_attention takes, read in place."""
+    if not isinstance(qkv, torch.Tensor) or qkv.dim() != 3:
+        raise ValueError("self_attention_probe: qkv must be a (B, L, 3 * heads * head_dim) tensor")
+    H, D = int(num_heads), int(head_dim)
+    if H < 1 or D < 1 or qkv.shape[2] != 3 * H * D:
+        raise ValueError(f"self_attention_probe: qkv width {qkv.shape[2]} is not 3 * {H} heads * {D}")
+    if qkv.dtype != BF16:
+        raise ValueError(f"self_attention_probe: qkv must be bf16 (the buffer the attention kernels read), got {qkv.dtype}")
+    if not qkv.is_contiguous():
+        qkv = qkv.contiguous()
+    B, L = qkv.shape[:2]
+    v5 = qkv.detach().view(B, L, 3, H, D)
+    scale = (1.0 / math.sqrt(float(D))) if scale is None else scale
+    return attention_probe(v5[:, :, 0], v5[:, :, 1], rows, scale=scale, mask_tables=mask_tables, per_head=per_head)
+
+
+class AttentionProbe:
+    """What a forward is asked to report: `rows` (B, R) int32 on the device -- the query rows of every sequence -- or None for
+    every query row (the resampler's latents), and `layers`, the indices of the attention layers to report (None = all).  The
+    modules that take `probe=` (GPT2Model, PerceiverResampler) call `record` from each selected layer on the q / k it has just
+    computed; after the forward `maps` is (B, n_layers, R, Lk) fp32, the head mean ((B, n_layers, H, R, Lk) with per_head),
+    layers in the order they ran."""
+
+    def __init__(self, rows=None, layers=None, per_head=False):
+        if rows is not None and (not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 2):
+            raise ValueError("AttentionProbe: rows must be an int32 (B, R) tensor or None (every query row)")
+        self.rows = rows
+        self.layers = None if layers is None else tuple(int(i) for i in layers)
+        self.per_head = bool(per_head)
+        self.maps = None
+        self._got = []
+
+    def begin(self, module):
+        """called by the module that was handed the probe, before its first layer"""
+        if module.training:
+            raise RuntimeError("an attention probe needs eval(): in training mode dropout is applied to the probabilities, and the "
+                               "map would not be what the forward used")
+        self.maps, self._got = None, []
+
+    def wants(self, layer_idx):
+        return self.layers is None or layer_idx in self.layers
+
+    def _rows_for(self, B, Lq, device):
+        if self.rows is not None:
+            return self.rows
+        if Lq > PROBE_MAX_ROWS:
+            raise ValueError(f"AttentionProbe(rows=None) reports every query row: {Lq} rows, at most {PROBE_MAX_ROWS}")
+        return torch.arange(Lq, dtype=torch.int32, device=device).unsqueeze(0).expand(B, Lq).contiguous()
+
+    def record(self, q, k, *, scale, mask_tables=None):
+        self._got.append(attention_probe(q, k, self._rows_for(q.shape[0], q.shape[1], q.device), scale=scale,
+                                         mask_tables=mask_tables, per_head=self.per_head))
+
+    def record_packed(self, qkv, num_heads, head_dim, *, scale, mask_tables=None):
+        self._got.append(self_attention_probe(qkv, num_heads, self._rows_for(qkv.shape[0], qkv.shape[1], qkv.device), scale=scale,
+                                              mask_tables=mask_tables, per_head=self.per_head, head_dim=head_dim))
+
+    def end(self):
+        if not self._got:
+            raise ValueError(f"AttentionProbe: no attention layer matches layers={self.layers}")
+        self.maps = torch.stack(self._got, dim=1)
+        self._got = []
+        return self.maps
+
+
+def attention_mass(maps, groups, S):
+    """maps (..., R, S * blk): probe rows over a window of S frame blocks; groups: (name, start, count) of the token groups of
+    one block (DreamVLA.token_groups).  -> (..., R, S, n_groups): the share of each row's attention on each group of each window
+    step; sums to 1 over (S, groups) for a row that sees anything (the groups cover the block), to 0 otherwise.  Pure torch."""
+    S = int(S)
+    L = maps.shape[-1]
+    if S < 1 or L % S != 0:
+        raise ValueError(f"attention_mass: {L} columns are not {S} equal blocks")
+    blk = L // S
+    m = maps.reshape(*maps.shape[:-1], S, blk)
+    out = []
+    for name, start, count in groups:
+        if start < 0 or count < 0 or start + count > blk:
+            raise ValueError(f"attention_mass: group {name!r} ({start}, {count}) lies outside a block of {blk} tokens")
+        out.append(m[..., start:start + count].sum(dim=-1))
+    return torch.stack(out, dim=-1)
+
+
+def attention_rollout(resampler_maps, n_media):
+    """resampler_maps (N, n_layers, n_lat, n_media + n_lat), head-mean maps of the resampler's cross-attentions, columns = media
+    tokens then latents -> (N, n_lat, n_media): R_0 = 0, R_l = 0.5 R_{l-1} + 0.5 (M_l + T_l R_{l-1})."""
+    N, n_layers, n_lat, width = resampler_maps.shape
+    if width != n_media + n_lat:
+        raise ValueError(f"attention_rollout: {width} columns, expected {n_media} media + {n_lat} latent")
+    R = torch.zeros((N, n_lat, n_media), dtype=resampler_maps.dtype, device=resampler_maps.device)
+    for l in range(n_layers):
+        M, T = resampler_maps[:, l, :, :n_media], resampler_maps[:, l, :, n_media:]
+        # (T R as a broadcast product and a sum: 16 x 16 x 196 elements per frame, no library GEMM in an evaluation step's graph)
+        R = 0.5 * R + 0.5 * (M + (T.unsqueeze(-1) * R.unsqueeze(-3)).sum(dim=-2))
+    return R
+
+
+def patch_heat(trunk_maps, resampler_maps, groups, position):
+    """A patch heat map per camera for the frame at window position `position` (int, or a (B,) int64 tensor: one per sequence).
+    trunk_maps (B, n_layers, R, S * blk) from the trunk probe; resampler_maps (2 * B * F, n_res_layers, n_lat, n_patch + n_lat)
+    as DreamVLA.encode_frames leaves them -- the primary views of all B * F frames, then the wrist views -- with F = 1 (the frame
+    at `position` alone, as the rollout engine keeps it) or F = S (the whole window: the frame at `position` is picked); groups as
+    for attention_mass, with "image_primary" / "image_wrist" of n_lat tokens each.  heat[b, v] = sum_i w_i rollout[v, b, i], w_i = the trunk mass of the rows on image token i of view v at
+    `position`, averaged over rows and layers; normalised to sum 1 per view, all zeros when the mass is 0.  -> (B, 2, g, g) with
+    g * g = n_patch.  A heuristic attribution: it stops at the ViT's output tokens.  Pure torch."""
+    B, _, _, L = trunk_maps.shape
+    if resampler_maps.dim() != 4 or resampler_maps.shape[0] % (2 * B) != 0:
+        raise ValueError(f"patch_heat: resampler_maps must be (2 * {B} * frames, layers, latents, patches + latents)")
+    n_lat = resampler_maps.shape[2]
+    n_patch = resampler_maps.shape[3] - n_lat
+    g = int(round(math.sqrt(n_patch)))
+    if n_patch < 1 or g * g != n_patch:
+        raise ValueError(f"patch_heat: {n_patch} patch columns are not a square grid")
+    by_name = {name: (start, count) for name, start, count in groups}
+    blk = max(start + count for _, start, count in groups)
+    if L % blk != 0:
+        raise ValueError(f"patch_heat: {L} trunk columns are not whole blocks of {blk} tokens")
+    pos = torch.as_tensor(position, dtype=torch.long, device=trunk_maps.device).expand(B)
+    w_all = trunk_maps.mean(dim=(1, 2)).reshape(B, L // blk, blk)                # (B, S, blk)
+    bi = torch.arange(B, device=trunk_maps.device)
+    w_at = w_all[bi, pos]                                                        # (B, blk)
+    F = resampler_maps.shape[0] // (2 * B)
+    if F not in (1, L // blk):
+        raise ValueError(f"patch_heat: resampler maps of {F} frames per sequence; 1 or the window's {L // blk} expected")
+    res = resampler_maps.reshape(2, B, F, *resampler_maps.shape[1:])
+    res = res[:, :, 0] if F == 1 else res[:, bi, pos]                            # (2, B, layers, n_lat, n_patch + n_lat)
+    heat = []
+    for v, name in enumerate(("image_primary", "image_wrist")):
+        start, count = by_name[name]
+        if count != n_lat:
+            raise ValueError(f"patch_heat: group {name!r} has {count} tokens, the resampler maps {n_lat} latents")
+        roll = attention_rollout(res[v], n_patch)                     # (B, n_lat, n_patch)
+        hv = (w_at[:, start:start + count].to(roll.dtype).unsqueeze(-1) * roll).sum(dim=1)
+        tot = hv.sum(dim=-1, keepdim=True)
+        heat.append(torch.where(tot > 0, hv / torch.where(tot > 0, tot, torch.ones_like(tot)), torch.zeros_like(hv)))
+    return torch.stack(heat, dim=1).view(B, 2, g, g)
+
+
+# ---------------------------------------------------------------------------------------------------
 # autograd Functions
 # ---------------------------------------------------------------------------------------------------
 # fp32 masters, bf16 compute (the shipped scripts: `--precision fp32 --bf16_module vision_encoder`,

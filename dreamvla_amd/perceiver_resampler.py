@@ -41,9 +41,9 @@ class PerceiverAttention(nn.Module):
         self.to_kv = Linear(dim, inner_dim * 2, bias=False)
         self.to_out = Linear(inner_dim, dim, bias=False)
 
-    def forward(self, x, latents):
+    def forward(self, x, latents, probe=None):
         """x: (n, n1, D) media tokens, latents: (n, n2, D).  Returns latents + attention (the residual add is fused
-        into the to_out GEMM epilogue)."""
+        into the to_out GEMM epilogue).  `probe`: an ops.AttentionProbe that records this layer's map (n2 x (n1 + n2))."""
         # the two LayerNorms write the two row ranges of ONE (n, n1 + n2, D) buffer: no torch.cat, and in backward no copies of
         # the cat's strided gradient slices (ops._LayerNormConcat).  The queries take their own LayerNorm of the 16 latents
         # (a second, tiny launch): slicing them out of the buffer would send a zero-filled (n, n1 + n2, D) gradient back into it.
@@ -51,6 +51,10 @@ class PerceiverAttention(nn.Module):
                                      latents, self.norm_latents.weight, self.norm_latents.bias, self.norm_latents.eps)
         q = self.to_q(self.norm_latents(latents))
         kv = self.to_kv(both)
+        if probe is not None:      # reads the q and the k half of the kv that the attention below reads
+            n, Lq, Lk = q.shape[0], q.shape[1], kv.shape[1]
+            qc, kvc = ops.to_compute(q).detach().contiguous(), ops.to_compute(kv).detach().contiguous()
+            probe.record(qc.view(n, Lq, self.heads, 64), kvc.view(n, Lk, 2, self.heads, 64)[:, :, 0], scale=self.scale)
         o = ops.cross_attention(q, kv, self.heads, scale=self.scale)
         return self.to_out(o, residual=latents)
 
@@ -68,8 +72,12 @@ class PerceiverResampler(nn.Module):
                                               FeedForward(dim=dim, mult=ff_mult)]))
         self.norm = LayerNorm(dim)
 
-    def forward(self, x):
-        """x: (b, T, F, v, D) -> (b, T, num_latents, D)"""
+    def forward(self, x, probe=None):
+        """x: (b, T, F, v, D) -> (b, T, num_latents, D).  `probe` (an addition; eval() only): an ops.AttentionProbe, normally
+        AttentionProbe() = every latent row of every layer; `probe.maps` is (b * T, depth, num_latents, F * v + num_latents)
+        afterwards, columns = media tokens then latents.  The output does not depend on it."""
+        if probe is not None:
+            probe.begin(self)
         b, T, F, v = x.shape[:4]
         if exists(self.frame_embs):
             x = x + self.frame_embs[:F].view(1, 1, F, 1, -1)
@@ -79,8 +87,10 @@ class PerceiverResampler(nn.Module):
         D = x.shape[-1]
         xm = x.reshape(b * T, F * v, D)
         latents = self.latents.to(x.dtype).unsqueeze(0).expand(b * T, -1, -1).contiguous()
-        for attn, ff in self.layers:
-            latents = attn(xm, latents)
+        for i, (attn, ff) in enumerate(self.layers):
+            latents = attn(xm, latents, probe=probe if probe is not None and probe.wants(i) else None)
             h = ff[0](latents)
             latents = ops.mlp(h, ff[1].weight, None, ff[3].weight, None, act="gelu_erf", residual=latents)
+        if probe is not None:
+            probe.end()
         return self.norm(latents).view(b, T, -1, D)

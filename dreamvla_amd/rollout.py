@@ -25,6 +25,10 @@ over independent episodes) and removes the redundant work:
     engine keeps both on the device and scores them there (csrc/dream_score.hip), next to the persistence baseline:
     `last_dream_scores`.
 
+  * attention maps (opt-in, `attention=`; an addition): the newest-frame encode and the decode also report where the selected trunk
+    rows -- by default the executed position's action queries -- look (csrc/attention_probe.hip), as further outputs of the same
+    graphs; `last_attention` holds the maps, their mass per token group and window step, and a patch heat map per camera.
+
 Episodes of one batch advance in lock-step (one `step` = one control step of every episode); `reset(mask)` restarts
 the episodes selected by a boolean mask (their history is cleared, the others keep theirs).
 """
@@ -81,7 +85,7 @@ class _Graphed:
 
 class RolloutEngine:
     def __init__(self, model, batch_size, history_len=None, use_graph=True, warmup_decodes=3, sample="newest", text="latched",
-                 dreams=(), score_dreams=False, horizon=3):
+                 dreams=(), score_dreams=False, horizon=3, attention=None):
         self.model = model.module if hasattr(model, "module") else model
         m = self.model
         if m.training:
@@ -135,6 +139,21 @@ class RolloutEngine:
                 raise ValueError("score_dreams needs a model with pred_num == 1")
             if self.horizon < 1:
                 raise ValueError("horizon: the number of control steps a dream looks ahead, >= 1")
+        # Attention maps (opt-in, an addition: DESIGN.md section 5).  `attention`: None, or the spec of DreamVLA.decode_tokens,
+        # dict(rows="action" | "obs" | int (B, R) tensor, layers="all" | "last" | indices); "action" / "obs" mean the queries of the
+        # EXECUTED window position, whatever `sample` is: the rows are computed inside the decode from the same device tensor that
+        # feeds test_select, so one capture serves every step.  The newest-frame encode then also returns its resampler maps and the
+        # decode the trunk maps (further static outputs of the two graphs); `last_attention` is filled per step (see _attend).
+        # None: no tensors, no launches, the same graphs.
+        self.attention = None
+        self.last_attention = {}
+        self._res_maps = None                   # resampler maps of the newest frame, (2 B, depth, nq, 196 + nq)
+        if attention is not None:
+            DreamVLA._attention_probe(m, attention, self.B, self.S, torch.zeros(self.B, dtype=torch.long), "cpu")   # validates
+            self.attention = dict(rows=attention.get("rows", "action"), layers=attention.get("layers", "all"))
+            if torch.is_tensor(self.attention["rows"]):
+                self.attention["rows"] = self.attention["rows"].to(self.device, torch.int32).clone()
+            self._groups = DreamVLA.token_groups(m)
         self.since_reset = torch.zeros(self.B, dtype=torch.long)    # host: control steps of each episode since its last reset
         self._score_step = 0                    # control steps scored so far: slot `_score_step % horizon` of the rings is the oldest
         self._dream_ring = self._frame_ring = self._depth_ring = None   # (B, horizon, 2, n, n, 3) uint8 x 2, (B, horizon, 2, n, n) float32
@@ -176,8 +195,11 @@ class RolloutEngine:
         m = self.model
         with ops.forward_split_k():
             parts = m.encode_frames(image_primary.unsqueeze(1), image_wrist.unsqueeze(1), state.unsqueeze(1), None,
-                                    text_embedding=text_emb.view(text_emb.shape[0], 1, 1, -1))
-        return (torch.cat(parts, dim=2)[:, 0],)
+                                    text_embedding=text_emb.view(text_emb.shape[0], 1, 1, -1),
+                                    **({} if self.attention is None else dict(attention=self.attention)))
+        if self.attention is None:
+            return (torch.cat(parts, dim=2)[:, 0],)
+        return (torch.cat(parts, dim=2)[:, 0], m.last_attention["resampler"])
 
     @torch.no_grad()
     def text_embedding(self, text_token):
@@ -201,7 +223,10 @@ class RolloutEngine:
         """(B,3,224,224) x 2, (B,7|8), (B,77) int64 -> (B, 36, H) tokens of the newest frame (state encoders, ViT on both
         views, resampler, projectors: one hipGraph when use_graph; the text token comes from `text_embedding`)"""
         f = self._encode_g if self.use_graph else self._encode_eager
-        return f(image_primary.contiguous(), image_wrist.contiguous(), state.contiguous(), self.text_embedding(text_token))[0]
+        out = f(image_primary.contiguous(), image_wrist.contiguous(), state.contiguous(), self.text_embedding(text_token))
+        if self.attention is not None:
+            self._res_maps = out[1]
+        return out[0]
 
     def _push(self, new_tok, new_frames=None):
         """queue semantics of ModelWrapper.step: append; while an episode has seen k < S frames its window is
@@ -238,22 +263,30 @@ class RolloutEngine:
         self.count = torch.clamp(k + 1, max=S)
 
     # ------------------------------------------------------------------------------------------------------------
-    def _decode_eager(self, tokens, noise, sel, frames=None):
+    def _decode_eager(self, tokens, noise, sel, *more):
+        """`more`: the kept camera frames (with an image dream), then the newest frame's resampler maps (with `attention`)"""
+        more = list(more)
+        frames = more.pop(0) if "image" in self.dreams else None
+        res_maps = more.pop(0) if self.attention is not None else None
         am = getattr(self.model, "action_model", None)
         shared = getattr(am, "team_sampler", True) if am is not None else True
         before = getattr(am, "team_launches", 0) if am is not None else 0
         if am is not None:
             am.team_sampler = bool(shared) and self._team_allowed      # this engine's choice for the duration of ITS decode only
+        extra = {}
+        if self.attention is not None:        # the executed position's rows, from `sel` on the device
+            rows = self.model._attention_rows(self.attention["rows"], self.B, self.S, sel, tokens.device)
+            extra = dict(attention=dict(rows=rows, layers=self.attention["layers"]))
         try:
             with ops.forward_split_k():       # the trunk at one episode: 930 rows, K = 4096 in the MLP down-projection
                 if not self.dreams:
                     out = self.model.decode_tokens(tokens, mode="test", test_noise=noise if self.needs_noise else None,
-                                                   test_select=None if self.sample_all else sel)
+                                                   test_select=None if self.sample_all else sel, **extra)
                 else:
                     # (the MLP action head ignores test_select: with it the dream heads run on the executed position only)
                     out = self.model.decode_tokens(tokens, mode="test", test_noise=noise if self.needs_noise else None,
                                                    test_select=None if (self.sample_all and self.dreams_all) else sel,
-                                                   dreams=self.dreams)
+                                                   dreams=self.dreams, **extra)
         finally:
             if am is not None:
                 am.team_sampler = shared
@@ -261,7 +294,8 @@ class RolloutEngine:
                 self._team_in_decode = getattr(am, "team_launches", 0) > before
                 if self._team_in_decode:          # the workspace of the launch just made (DDIM or flow matching, any step count)
                     self._team_entry = getattr(am, "team_entry", None)
-        return (out[0], out[1], *self._render(out, frames))
+        maps = () if self.attention is None else self._attend(self.model.last_attention["trunk"], res_maps, sel)
+        return (out[0], out[1], *self._render(out, frames), *maps)
 
     _DREAM_SLOT = {"image": 2, "depth": 6, "traj": 7, "dino": 8, "sam": 9}       # positions in decode_tokens' 10-tuple
 
@@ -290,6 +324,8 @@ class RolloutEngine:
     @torch.no_grad()
     def _decode(self, tokens, noise, sel):
         args = (tokens, noise, sel) + ((self.frames,) if "image" in self.dreams else ())
+        if self.attention is not None:
+            args += (self._res_maps,)
         return (self._decode_g if self.use_graph else self._decode_eager)(*args)
 
     def draw_noise(self, generator=None):
@@ -443,8 +479,23 @@ class RolloutEngine:
             out = self._decode(self.tokens, noise, sel)
             action, arm, grip = self._actions(out[0], out[1], sel, bi)
         # the dreams of the decode whose action is returned (after a fallback: of the recomputed one)
-        self.last_dreams = dict(zip(self.dreams, out[2:]))
+        self.last_dreams = dict(zip(self.dreams, out[2:2 + len(self.dreams)]))
+        if self.attention is not None:
+            # `last_attention` of this step (of the decode whose action was returned):
+            #   "trunk"   (B, n_layers, R, L) fp32: the head-mean attention of the selected rows in the selected trunk layers
+            #   "mass"    (B, R, S, n_groups): its share per token group and window step, averaged over the layers; "groups": the names
+            #   "heat"    (B, 2, g, g): ops.patch_heat for the executed position's frame -- the newest real frame, whose resampler
+            #             maps ("resampler", (2 B, depth, nq, patches + nq)) the encode of this step produced
+            trunk, mass, heat = out[-3:]
+            self.last_attention = {"trunk": trunk, "mass": mass, "heat": heat, "groups": [g[0] for g in self._groups],
+                                   "resampler": self._res_maps}
         return action, arm, grip
+
+    def _attend(self, trunk, res_maps, sel):
+        """what the decode -- eager or the captured graph -- returns next to the actions: the trunk maps, their mass per token group
+        and window step, and the patch heat of the executed position's frame (small torch arithmetic, part of the same graph)"""
+        return (trunk, ops.attention_mass(trunk, self._groups, self.S).mean(dim=1),
+                ops.patch_heat(trunk, res_maps, self._groups, sel))
 
     def _actions(self, arm, grip, sel, bi):
         B, S = self.B, self.S

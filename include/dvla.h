@@ -259,6 +259,20 @@ int dvla_attn_small_bwd(const dvla_attn_params* p, int32_t head_dim, void* strea
  * o / dq / dk / dv are not written.  q / k / v / dout (and o in backward) need 16-byte aligned rows, o / dq / dk / dv 8-byte. */
 int dvla_attn_hd_fwd(const dvla_attn_params* p, int32_t head_dim, void* stream);
 int dvla_attn_hd_bwd(const dvla_attn_params* p, int32_t head_dim, void* stream);
+/* (additive, still ABI 9) Attention probe: the softmax probabilities of R selected query rows of every sequence over all keys --
+ * what the kernels above apply and never store.  An evaluation instrument with no counterpart in the reference.
+ * Of the parameter block it reads q, k and their strides, B, H, Lq, Lk, scale, key_index and mask_bits_q (NULL = no mask;
+ * key_index NULL = keys in place, Lk == Lk_full); v, o, dropout and everything after are ignored.  head_dim: a multiple of 8 from
+ * 8 to 128, 64 included.  rows: (B, R) int32 on the device, 1 <= R <= DVLA_PROBE_MAX_ROWS (DVLA_ERR_UNSUPPORTED otherwise, before
+ * any launch); an entry < 0 or >= Lq gives a zero row.
+ * out (fp32): per_head != 0: (B, H, R, Lk_full);  per_head == 0: (B, R, Lk_full), the mean over heads = (sum over h ascending) / H,
+ * and workspace must hold B * H * R * Lk_full floats.  Columns are ORIGINAL key numbers (key_index is undone on the store).  Every
+ * element of out is written: a key the row cannot see, and a row that sees no key, get exactly 0.0f.
+ * p = exp(s - max s) / sum exp(s - max s) over the visible keys, s = scale * <q, k> accumulated in fp32.  No atomics, no host
+ * synchronisation; a sequence's result does not depend on B or on its place in the batch and is the same bits on every run. */
+#define DVLA_PROBE_MAX_ROWS 32
+int dvla_attn_probe(const dvla_attn_params* p, const int32_t* rows, int32_t R, int32_t head_dim, int32_t Lk_full, int32_t per_head,
+                    float* out, float* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Small HBM-bound helpers (bf16 unless noted).
