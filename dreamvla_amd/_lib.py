@@ -227,6 +227,16 @@ SYMBOLS = {
     "dvla_segment_adam_bf16": (C.c_int, [_P, _P, _I64, _P, _I64, _P, C.c_float, C.c_float, _I64, _P]),
     "dvla_segment_adam_f32": (C.c_int, [_P, _P, _I64, _P, _I64, _P, C.c_double, C.c_double, _I64, _P]),
     "dvla_segment_combine": (C.c_int, [_P, _I64, _P, _I32, _P, _P, _P, _I64, _P]),
+    "dvla_group_sumsq": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P]),
+    "dvla_adamw_bf16_grouped_clip": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P, _I32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                               C.c_float, C.c_float, C.c_float, _I64, _P, C.POINTER(C.c_float), _P,
+                                               C.POINTER(C.c_float), _I32, _P]),
+    "dvla_adamw_f32_master_grouped_clip": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _P, _I32, C.POINTER(C.c_double),
+                                                     C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, _I64, _P,
+                                                     C.POINTER(C.c_float), _P, C.POINTER(C.c_float), _I32, _P]),
+    "dvla_adamw_bf16_sr_clip": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P, _I32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                          C.c_float, C.c_float, C.c_float, _I64, _P, C.POINTER(C.c_float), _P, C.POINTER(C.c_float),
+                                          _I32, C.c_uint64, _I32, _I64, _P]),
 }
 
 _lib = None

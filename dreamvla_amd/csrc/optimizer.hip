@@ -535,14 +535,36 @@ __device__ __forceinline__ float clip_coef(const float* sumsq, float max_norm) {
   return c < 1.0f ? c : 1.0f;
 }
 
+// Per-group clipping (CLIP; dvla.h: dvla_adamw_*_clip): the groups' sums of squares stay in device memory, their max_norm travel by
+// value, and wave 0 puts one coefficient per group -- clip_coef itself on (&sumsq[g], max_norm[g]) -- into LDS next to the group's
+// row.  Without CLIP the struct is empty and the LAST kernel argument, and every `if (CLIP)` folds away: the kernels of the
+// entry points without `_clip` keep their instruction streams.
+template <bool CLIP> struct ClipTab {};
+template <> struct ClipTab<true> { const float* sumsq; float max_norm[DVLA_STEP_MAX_GROUPS]; };
+
+// the coefficient of group threadIdx.x; `off` for a group that is not clipped (max_norm <= 0 or NaN: its sum is not read)
+__device__ __forceinline__ float group_coef(const ClipTab<true>& c, int n_groups, float off) {
+  float mx = 0.f;
+#pragma unroll
+  for (int g = 0; g < DVLA_STEP_MAX_GROUPS; ++g) {
+    if (g >= n_groups) break;                                        // uniform, as in group_row
+    if ((int)threadIdx.x == g) mx = c.max_norm[g];
+  }
+  return mx > 0.f ? clip_coef(c.sumsq + threadIdx.x, mx) : off;
+}
+__device__ __forceinline__ float group_coef(const ClipTab<false>&, int, float off) { return off; }
+
 // GUARD: the verdict and the step-dependent scalars come from *st (adamw_master_guarded_kernel); EMA: + ema_one on the
 // parameter just written (adamw_master_ema_body).  Every element goes through master_one, on a copy of the arguments that
-// carries its group's decay and step_size.
-template <bool GUARD, bool EMA>
+// carries its group's decay and step_size -- CLIP: and its group's clip, sumsq null for a group that is not clipped (coefficient
+// < 0 in LDS), as the one-group entry point gets it.
+template <bool GUARD, bool EMA, bool CLIP = false>
 __global__ __launch_bounds__(256) void adamw_master_grouped_kernel(MasterArgs a, const uint8_t* __restrict__ map, int n_groups,
                                                                    GroupTab<GUARD ? DVLA_STEP_MAX_CANDIDATES : 1> t, float* ema,
-                                                                   EmaTable wt, const dvla_step_state* __restrict__ st) {
+                                                                   EmaTable wt, const dvla_step_state* __restrict__ st,
+                                                                   ClipTab<CLIP> ct) {
   __shared__ float2 rows[DVLA_STEP_MAX_GROUPS];
+  __shared__ float coefs[CLIP ? DVLA_STEP_MAX_GROUPS : 1];
   int cand = 0;
   if (GUARD) {
     if (st->ok == 0) return;
@@ -550,9 +572,13 @@ __global__ __launch_bounds__(256) void adamw_master_grouped_kernel(MasterArgs a,
     cand = st->cand;
   }
   if (threadIdx.x < DVLA_STEP_MAX_GROUPS) rows[threadIdx.x] = group_row(t, n_groups, cand);
+  if (CLIP) {
+    if (threadIdx.x < DVLA_STEP_MAX_GROUPS) coefs[threadIdx.x] = group_coef(ct, n_groups, -1.0f);
+  }
   __syncthreads();
   const EmaArgs x = ema_args(ema, EMA ? ema_pick(wt, cand) : 0.f);
-  const float coef = clip_coef(a.sumsq, a.max_norm);
+  float coef = 1.0f;
+  if (!CLIP) coef = clip_coef(a.sumsq, a.max_norm);
   const int64_t nvec = a.n >> 3, stride = (int64_t)gridDim.x * 256;
   int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   unsigned id = i < nvec ? map[i] : 255u;
@@ -563,6 +589,7 @@ __global__ __launch_bounds__(256) void adamw_master_grouped_kernel(MasterArgs a,
       const float2 r = rows[id];
       MasterArgs b = a;
       b.decay = r.x; b.step_size = r.y;
+      if constexpr (CLIP) { coef = coefs[id]; b.sumsq = coef < 0.f ? nullptr : ct.sumsq; }
       float4 p4[2], g4[2], m4[2], v4[2], e4[2];
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -596,6 +623,7 @@ __global__ __launch_bounds__(256) void adamw_master_grouped_kernel(MasterArgs a,
       const float2 r = rows[idt];
       MasterArgs b = a;
       b.decay = r.x; b.step_size = r.y;
+      if constexpr (CLIP) { coef = coefs[idt]; b.sumsq = coef < 0.f ? nullptr : ct.sumsq; }
       for (int64_t j = (nvec << 3) + threadIdx.x; j < a.n; j += 256) {
         float p = a.p[j], m = a.m[j], v = a.v[j];
         master_one(p, a.g[j], m, v, b, coef);
@@ -626,10 +654,13 @@ __device__ __forceinline__ void adam_group_one(float& p, float g, float& m, floa
   p = TAIL ? (1.0f - lr * wd) * p - q : fmaf(fmaf(-lr, wd, 1.0f), p, -q);
 }
 
-template <bool GUARD, bool EMA>
+// CLIP: the coefficient is the group's (1 for a group that is not clipped: adam_one multiplies by 1 without a clip as well).
+template <bool GUARD, bool EMA, bool CLIP = false>
 __global__ __launch_bounds__(256) void adamw_grouped_kernel(AdamArgs a, const uint8_t* __restrict__ map, int n_groups, GroupTab<1> t,
-                                                            float* ema, EmaTable wt, const dvla_step_state* __restrict__ st) {
+                                                            float* ema, EmaTable wt, const dvla_step_state* __restrict__ st,
+                                                            ClipTab<CLIP> ct) {
   __shared__ float2 rows[DVLA_STEP_MAX_GROUPS];
+  __shared__ float coefs[CLIP ? DVLA_STEP_MAX_GROUPS : 1];
   int cand = 0;
   if (GUARD) {
     if (st->ok == 0) return;
@@ -637,9 +668,13 @@ __global__ __launch_bounds__(256) void adamw_grouped_kernel(AdamArgs a, const ui
     cand = st->cand;
   }
   if (threadIdx.x < DVLA_STEP_MAX_GROUPS) rows[threadIdx.x] = group_row(t, n_groups, 0);
+  if (CLIP) {
+    if (threadIdx.x < DVLA_STEP_MAX_GROUPS) coefs[threadIdx.x] = group_coef(ct, n_groups, 1.0f);
+  }
   __syncthreads();
   const EmaArgs x = ema_args(ema, EMA ? ema_pick(wt, cand) : 0.f);
-  const float coef = clip_coef(a.sumsq, a.max_norm);
+  float coef = 1.0f;
+  if (!CLIP) coef = clip_coef(a.sumsq, a.max_norm);
   const int64_t nvec = a.n >> 3, stride = (int64_t)gridDim.x * 256;
   int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   unsigned id = i < nvec ? map[i] : 255u;
@@ -648,6 +683,7 @@ __global__ __launch_bounds__(256) void adamw_grouped_kernel(AdamArgs a, const ui
     const unsigned id_nx = nx < nvec ? map[nx] : 255u;
     if (id < (unsigned)n_groups) {
       const float2 r = rows[id];      // lr, wd
+      if (CLIP) coef = coefs[id];
       const uint4 up = reinterpret_cast<const uint4*>(a.p)[i], ug = reinterpret_cast<const uint4*>(a.g)[i];
       const uint4 um = reinterpret_cast<const uint4*>(a.m)[i], uv = reinterpret_cast<const uint4*>(a.v)[i];
       float4 e0, e1;
@@ -684,6 +720,7 @@ __global__ __launch_bounds__(256) void adamw_grouped_kernel(AdamArgs a, const ui
     const unsigned idt = map[nvec];
     if (idt < (unsigned)n_groups) {
       const float2 r = rows[idt];
+      if (CLIP) coef = coefs[idt];
       for (int64_t j = (nvec << 3) + threadIdx.x; j < a.n; j += 256) {
         float p = bf2f(a.p[j]), m = bf2f(a.m[j]), v = bf2f(a.v[j]);
         adam_group_one<true>(p, bf2f(a.g[j]), m, v, a, r.x, r.y, coef);
@@ -736,10 +773,14 @@ struct SrArgs { uint64_t seed; int64_t step, base; uint32_t bucket; };      // s
 // adamw_grouped_kernel with the three final conversions rounded stochastically: the same element function (adam_group_one, so
 // the fp32 values are those of every other bf16 step kernel), the same guard, EMA (on the parameter as stored) and map.
 // MAP false: no map, one group (row 0 of the table) over all n elements -- the one-group step over a range of a bucket.
-template <bool GUARD, bool EMA, bool MAP>
+// CLIP (with MAP only): the coefficient per group, as in adamw_grouped_kernel.
+template <bool GUARD, bool EMA, bool MAP, bool CLIP = false>
 __global__ __launch_bounds__(256) void adamw_sr_kernel(AdamArgs a, const uint8_t* __restrict__ map, int n_groups, GroupTab<1> t,
-                                                       float* ema, EmaTable wt, const dvla_step_state* __restrict__ st, SrArgs sr) {
+                                                       float* ema, EmaTable wt, const dvla_step_state* __restrict__ st, SrArgs sr,
+                                                       ClipTab<CLIP> ct) {
+  static_assert(MAP || !CLIP, "a coefficient per group needs the group map");
   __shared__ float2 rows[DVLA_STEP_MAX_GROUPS];
+  __shared__ float coefs[CLIP ? DVLA_STEP_MAX_GROUPS : 1];
   int cand = 0;
   if (GUARD) {
     if (st->ok == 0) return;
@@ -749,11 +790,15 @@ __global__ __launch_bounds__(256) void adamw_sr_kernel(AdamArgs a, const uint8_t
   const uint32_t key = sr_key(sr.seed, GUARD ? (uint64_t)st->applied : (uint64_t)sr.step, sr.bucket);
   if (MAP) {
     if (threadIdx.x < DVLA_STEP_MAX_GROUPS) rows[threadIdx.x] = group_row(t, n_groups, 0);
+    if (CLIP) {
+      if (threadIdx.x < DVLA_STEP_MAX_GROUPS) coefs[threadIdx.x] = group_coef(ct, n_groups, 1.0f);
+    }
     __syncthreads();
   }
   const float2 r0 = make_float2(t.x[0], t.y[0][0]);
   const EmaArgs x = ema_args(ema, EMA ? ema_pick(wt, cand) : 0.f);
-  const float coef = clip_coef(a.sumsq, a.max_norm);
+  float coef = 1.0f;
+  if (!CLIP) coef = clip_coef(a.sumsq, a.max_norm);
   const int64_t nvec = a.n >> 3, stride = (int64_t)gridDim.x * 256;
   int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   unsigned id = 0;
@@ -764,6 +809,7 @@ __global__ __launch_bounds__(256) void adamw_sr_kernel(AdamArgs a, const uint8_t
     if (MAP) id_nx = nx < nvec ? map[nx] : 255u;
     if (id < (unsigned)n_groups) {
       const float2 r = MAP ? rows[id] : r0;      // lr, wd
+      if (CLIP) coef = coefs[id];
       const uint4 up = reinterpret_cast<const uint4*>(a.p)[i], ug = reinterpret_cast<const uint4*>(a.g)[i];
       const uint4 um = reinterpret_cast<const uint4*>(a.m)[i], uv = reinterpret_cast<const uint4*>(a.v)[i];
       float4 e0, e1;
@@ -804,6 +850,7 @@ __global__ __launch_bounds__(256) void adamw_sr_kernel(AdamArgs a, const uint8_t
     const unsigned idt = MAP ? map[nvec] : 0u;
     if (idt < (unsigned)n_groups) {
       const float2 r = MAP ? rows[idt] : r0;
+      if (CLIP) coef = coefs[idt];
       for (int64_t j = (nvec << 3) + threadIdx.x; j < a.n; j += 256) {
         float p = bf2f(a.p[j]), m = bf2f(a.m[j]), v = bf2f(a.v[j]);
         adam_group_one<true>(p, bf2f(a.g[j]), m, v, a, r.x, r.y, coef);
@@ -1114,16 +1161,24 @@ inline void group_tab(GroupTab<NC>& t, const dvla_group_row* rows, int32_t n_gro
   }
 }
 
-}  // namespace
+// the per-group clip of the `_clip` entry points: null (the entry points without it: one coefficient per launch) or both given
+struct GroupClip { const float* sumsq; const float* max_norm; };
 
-extern "C" int dvla_adamw_bf16_grouped(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, float* ema, int64_t n,
-                                       const uint8_t* group_map, int32_t n_groups, const double* lr, const double* weight_decay,
-                                       float beta1, float beta2, float eps, int64_t step, const float* grad_sumsq, float max_norm,
-                                       const dvla_step_state* state, const float* ema_w, int32_t n_cand, void* stream_) {
+inline void clip_tab(ClipTab<true>& c, const GroupClip& clip, int32_t n_groups) {
+  c.sumsq = clip.sumsq;
+  for (int g = 0; g < DVLA_STEP_MAX_GROUPS; ++g) c.max_norm[g] = g < n_groups ? clip.max_norm[g] : 0.f;
+}
+
+// dvla_adamw_bf16_grouped and, with `clip`, dvla_adamw_bf16_grouped_clip
+int bf16_grouped(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, float* ema, int64_t n, const uint8_t* group_map,
+                 int32_t n_groups, const double* lr, const double* weight_decay, float beta1, float beta2, float eps, int64_t step,
+                 const float* grad_sumsq, float max_norm, const GroupClip* clip, const dvla_step_state* state, const float* ema_w,
+                 int32_t n_cand, void* stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   int rc = grouped_args(param && grad && exp_avg && exp_avg_sq, n, group_map, n_groups, lr, weight_decay, step, state, ema, ema_w,
                         n_cand);
   if (rc != DVLA_OK) return rc;
+  if (clip && (!clip->sumsq || !clip->max_norm)) return DVLA_ERR_ARG;
   if (n == 0) return DVLA_OK;
   if (!al16(param) || !al16(grad) || !al16(exp_avg) || !al16(exp_avg_sq) || (ema && !al16(ema)) || (state && !al16(state)))
     return DVLA_ERR_UNSUPPORTED;
@@ -1144,22 +1199,36 @@ extern "C" int dvla_adamw_bf16_grouped(void* param, const void* grad, void* exp_
   EmaTable w;
   if (ema) ema_table(w, ema_w, n_cand); else for (float& x : w.w) x = 0.f;
   const dim3 grid(step_blocks(n)), block(256);
-  if (state && ema) hipLaunchKernelGGL((adamw_grouped_kernel<true, true>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state);
-  else if (state) hipLaunchKernelGGL((adamw_grouped_kernel<true, false>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state);
-  else if (ema) hipLaunchKernelGGL((adamw_grouped_kernel<false, true>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state);
-  else hipLaunchKernelGGL((adamw_grouped_kernel<false, false>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state);
+#define DVLA_GROUPED_LAUNCH(G, E, C, ct)                                                                                       \
+  hipLaunchKernelGGL((adamw_grouped_kernel<G, E, C>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state, ct)
+  if (clip) {
+    ClipTab<true> c;
+    clip_tab(c, *clip, n_groups);
+    if (state && ema) DVLA_GROUPED_LAUNCH(true, true, true, c);
+    else if (state) DVLA_GROUPED_LAUNCH(true, false, true, c);
+    else if (ema) DVLA_GROUPED_LAUNCH(false, true, true, c);
+    else DVLA_GROUPED_LAUNCH(false, false, true, c);
+  } else {
+    const ClipTab<false> c{};
+    if (state && ema) DVLA_GROUPED_LAUNCH(true, true, false, c);
+    else if (state) DVLA_GROUPED_LAUNCH(true, false, false, c);
+    else if (ema) DVLA_GROUPED_LAUNCH(false, true, false, c);
+    else DVLA_GROUPED_LAUNCH(false, false, false, c);
+  }
+#undef DVLA_GROUPED_LAUNCH
   return dvla_check_launch();
 }
 
-extern "C" int dvla_adamw_f32_master_grouped(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
-                                             float* ema, int64_t n, const uint8_t* group_map, int32_t n_groups, const double* lr,
-                                             const double* weight_decay, double beta1, double beta2, double eps, int64_t step,
-                                             const float* grad_sumsq, float max_norm, const dvla_step_state* state,
-                                             const float* ema_w, int32_t n_cand, void* stream_) {
+// dvla_adamw_f32_master_grouped and, with `clip`, dvla_adamw_f32_master_grouped_clip
+int master_grouped(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, float* ema, int64_t n,
+                   const uint8_t* group_map, int32_t n_groups, const double* lr, const double* weight_decay, double beta1,
+                   double beta2, double eps, int64_t step, const float* grad_sumsq, float max_norm, const GroupClip* clip,
+                   const dvla_step_state* state, const float* ema_w, int32_t n_cand, void* stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   int rc = grouped_args(param && grad && exp_avg && exp_avg_sq, n, group_map, n_groups, lr, weight_decay, step, state, ema, ema_w,
                         n_cand);
   if (rc != DVLA_OK) return rc;
+  if (clip && (!clip->sumsq || !clip->max_norm)) return DVLA_ERR_ARG;
   if (n == 0) return DVLA_OK;
   if (!al16(param) || !al16(grad) || !al16(exp_avg) || !al16(exp_avg_sq) || (shadow_bf16 && !al16(shadow_bf16)) ||
       (ema && !al16(ema)) || (state && !al16(state)))
@@ -1176,18 +1245,66 @@ extern "C" int dvla_adamw_f32_master_grouped(float* param, const float* grad, fl
   EmaTable w;
   if (ema) ema_table(w, ema_w, n_cand); else for (float& x : w.w) x = 0.f;
   const dim3 grid(step_blocks(n)), block(256);
+  ClipTab<true> c;
+  if (clip) clip_tab(c, *clip, n_groups);
+  const ClipTab<false> none{};
+#define DVLA_MASTER_LAUNCH(G, E)                                                                                               \
+  if (clip) hipLaunchKernelGGL((adamw_master_grouped_kernel<G, E, true>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, \
+                               state, c);                                                                                      \
+  else hipLaunchKernelGGL((adamw_master_grouped_kernel<G, E, false>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w,  \
+                          state, none)
   if (state) {
     GroupTab<DVLA_STEP_MAX_CANDIDATES> t;
     group_tab(t, rows, n_groups, true);
-    if (ema) hipLaunchKernelGGL((adamw_master_grouped_kernel<true, true>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state);
-    else hipLaunchKernelGGL((adamw_master_grouped_kernel<true, false>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state);
+    if (ema) { DVLA_MASTER_LAUNCH(true, true); } else { DVLA_MASTER_LAUNCH(true, false); }
   } else {
     GroupTab<1> t;
     group_tab(t, rows, n_groups, true);
-    if (ema) hipLaunchKernelGGL((adamw_master_grouped_kernel<false, true>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state);
-    else hipLaunchKernelGGL((adamw_master_grouped_kernel<false, false>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state);
+    if (ema) { DVLA_MASTER_LAUNCH(false, true); } else { DVLA_MASTER_LAUNCH(false, false); }
   }
+#undef DVLA_MASTER_LAUNCH
   return dvla_check_launch();
+}
+
+}  // namespace
+
+extern "C" int dvla_adamw_bf16_grouped(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, float* ema, int64_t n,
+                                       const uint8_t* group_map, int32_t n_groups, const double* lr, const double* weight_decay,
+                                       float beta1, float beta2, float eps, int64_t step, const float* grad_sumsq, float max_norm,
+                                       const dvla_step_state* state, const float* ema_w, int32_t n_cand, void* stream) {
+  return bf16_grouped(param, grad, exp_avg, exp_avg_sq, ema, n, group_map, n_groups, lr, weight_decay, beta1, beta2, eps, step,
+                      grad_sumsq, max_norm, nullptr, state, ema_w, n_cand, stream);
+}
+
+extern "C" int dvla_adamw_f32_master_grouped(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
+                                             float* ema, int64_t n, const uint8_t* group_map, int32_t n_groups, const double* lr,
+                                             const double* weight_decay, double beta1, double beta2, double eps, int64_t step,
+                                             const float* grad_sumsq, float max_norm, const dvla_step_state* state,
+                                             const float* ema_w, int32_t n_cand, void* stream) {
+  return master_grouped(param, grad, exp_avg, exp_avg_sq, shadow_bf16, ema, n, group_map, n_groups, lr, weight_decay, beta1, beta2,
+                        eps, step, grad_sumsq, max_norm, nullptr, state, ema_w, n_cand, stream);
+}
+
+// ---- per-group clipping (additive, ABI 9) -----------------------------------------------------------------------------------
+extern "C" int dvla_adamw_bf16_grouped_clip(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, float* ema, int64_t n,
+                                            const uint8_t* group_map, int32_t n_groups, const double* lr,
+                                            const double* weight_decay, float beta1, float beta2, float eps, int64_t step,
+                                            const float* group_sumsq, const float* max_norm, const dvla_step_state* state,
+                                            const float* ema_w, int32_t n_cand, void* stream) {
+  const GroupClip clip = {group_sumsq, max_norm};
+  return bf16_grouped(param, grad, exp_avg, exp_avg_sq, ema, n, group_map, n_groups, lr, weight_decay, beta1, beta2, eps, step,
+                      nullptr, 0.f, &clip, state, ema_w, n_cand, stream);
+}
+
+extern "C" int dvla_adamw_f32_master_grouped_clip(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                                  void* shadow_bf16, float* ema, int64_t n, const uint8_t* group_map,
+                                                  int32_t n_groups, const double* lr, const double* weight_decay, double beta1,
+                                                  double beta2, double eps, int64_t step, const float* group_sumsq,
+                                                  const float* max_norm, const dvla_step_state* state, const float* ema_w,
+                                                  int32_t n_cand, void* stream) {
+  const GroupClip clip = {group_sumsq, max_norm};
+  return master_grouped(param, grad, exp_avg, exp_avg_sq, shadow_bf16, ema, n, group_map, n_groups, lr, weight_decay, beta1, beta2,
+                        eps, step, nullptr, 0.f, &clip, state, ema_w, n_cand, stream);
 }
 
 // ---- stochastic rounding (additive, ABI 9) ----------------------------------------------------------------------------------
@@ -1203,14 +1320,17 @@ extern "C" int dvla_sr_cast_f32_to_bf16(const float* x, void* out, int64_t n, ui
   return dvla_check_launch();
 }
 
-extern "C" int dvla_adamw_bf16_sr(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, float* ema, int64_t n,
-                                  const uint8_t* group_map, int32_t n_groups, const double* lr, const double* weight_decay,
-                                  float beta1, float beta2, float eps, int64_t step, const float* grad_sumsq, float max_norm,
-                                  const dvla_step_state* state, const float* ema_w, int32_t n_cand, uint64_t sr_seed,
-                                  int32_t sr_bucket, int64_t sr_index_base, void* stream_) {
+namespace {
+
+// dvla_adamw_bf16_sr and, with `clip` (and a map), dvla_adamw_bf16_sr_clip
+int bf16_sr(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, float* ema, int64_t n, const uint8_t* group_map,
+            int32_t n_groups, const double* lr, const double* weight_decay, float beta1, float beta2, float eps, int64_t step,
+            const float* grad_sumsq, float max_norm, const GroupClip* clip, const dvla_step_state* state, const float* ema_w,
+            int32_t n_cand, uint64_t sr_seed, int32_t sr_bucket, int64_t sr_index_base, void* stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   static const uint8_t no_map = 0;      // grouped_args wants a map; without one there is one group
-  if (!group_map && n_groups != 1) return DVLA_ERR_ARG;
+  if (!group_map && (n_groups != 1 || clip)) return DVLA_ERR_ARG;
+  if (clip && (!clip->sumsq || !clip->max_norm)) return DVLA_ERR_ARG;
   int rc = grouped_args(param && grad && exp_avg && exp_avg_sq, n, group_map ? group_map : &no_map, n_groups, lr, weight_decay, step,
                         state, ema, ema_w, n_cand);
   if (rc != DVLA_OK) return rc;
@@ -1237,18 +1357,51 @@ extern "C" int dvla_adamw_bf16_sr(void* param, const void* grad, void* exp_avg, 
   SrArgs sr;
   sr.seed = sr_seed; sr.step = step; sr.base = sr_index_base; sr.bucket = (uint32_t)sr_bucket;
   const dim3 grid(step_blocks(n)), block(256);
-#define DVLA_SR_LAUNCH(G, E, M)                                                                                                \
-  hipLaunchKernelGGL((adamw_sr_kernel<G, E, M>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state, sr)
+  const ClipTab<false> none{};
+#define DVLA_SR_LAUNCH(G, E, M, C, ct)                                                                                         \
+  hipLaunchKernelGGL((adamw_sr_kernel<G, E, M, C>), grid, block, 0, stream, a, group_map, n_groups, t, ema, w, state, sr, ct)
+  if (clip) {
+    ClipTab<true> c;
+    clip_tab(c, *clip, n_groups);
+    switch ((state ? 4 : 0) | (ema ? 2 : 0)) {
+      case 0: DVLA_SR_LAUNCH(false, false, true, true, c); break;
+      case 2: DVLA_SR_LAUNCH(false, true, true, true, c); break;
+      case 4: DVLA_SR_LAUNCH(true, false, true, true, c); break;
+      default: DVLA_SR_LAUNCH(true, true, true, true, c); break;
+    }
+    return dvla_check_launch();
+  }
   switch ((state ? 4 : 0) | (ema ? 2 : 0) | (group_map ? 1 : 0)) {
-    case 0: DVLA_SR_LAUNCH(false, false, false); break;
-    case 1: DVLA_SR_LAUNCH(false, false, true); break;
-    case 2: DVLA_SR_LAUNCH(false, true, false); break;
-    case 3: DVLA_SR_LAUNCH(false, true, true); break;
-    case 4: DVLA_SR_LAUNCH(true, false, false); break;
-    case 5: DVLA_SR_LAUNCH(true, false, true); break;
-    case 6: DVLA_SR_LAUNCH(true, true, false); break;
-    default: DVLA_SR_LAUNCH(true, true, true); break;
+    case 0: DVLA_SR_LAUNCH(false, false, false, false, none); break;
+    case 1: DVLA_SR_LAUNCH(false, false, true, false, none); break;
+    case 2: DVLA_SR_LAUNCH(false, true, false, false, none); break;
+    case 3: DVLA_SR_LAUNCH(false, true, true, false, none); break;
+    case 4: DVLA_SR_LAUNCH(true, false, false, false, none); break;
+    case 5: DVLA_SR_LAUNCH(true, false, true, false, none); break;
+    case 6: DVLA_SR_LAUNCH(true, true, false, false, none); break;
+    default: DVLA_SR_LAUNCH(true, true, true, false, none); break;
   }
 #undef DVLA_SR_LAUNCH
   return dvla_check_launch();
+}
+
+}  // namespace
+
+extern "C" int dvla_adamw_bf16_sr(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, float* ema, int64_t n,
+                                  const uint8_t* group_map, int32_t n_groups, const double* lr, const double* weight_decay,
+                                  float beta1, float beta2, float eps, int64_t step, const float* grad_sumsq, float max_norm,
+                                  const dvla_step_state* state, const float* ema_w, int32_t n_cand, uint64_t sr_seed,
+                                  int32_t sr_bucket, int64_t sr_index_base, void* stream) {
+  return bf16_sr(param, grad, exp_avg, exp_avg_sq, ema, n, group_map, n_groups, lr, weight_decay, beta1, beta2, eps, step, grad_sumsq,
+                 max_norm, nullptr, state, ema_w, n_cand, sr_seed, sr_bucket, sr_index_base, stream);
+}
+
+extern "C" int dvla_adamw_bf16_sr_clip(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, float* ema, int64_t n,
+                                       const uint8_t* group_map, int32_t n_groups, const double* lr, const double* weight_decay,
+                                       float beta1, float beta2, float eps, int64_t step, const float* group_sumsq,
+                                       const float* max_norm, const dvla_step_state* state, const float* ema_w, int32_t n_cand,
+                                       uint64_t sr_seed, int32_t sr_bucket, int64_t sr_index_base, void* stream) {
+  const GroupClip clip = {group_sumsq, max_norm};
+  return bf16_sr(param, grad, exp_avg, exp_avg_sq, ema, n, group_map, n_groups, lr, weight_decay, beta1, beta2, eps, step, nullptr,
+                 0.f, &clip, state, ema_w, n_cand, sr_seed, sr_bucket, sr_index_base, stream);
 }

@@ -9,6 +9,8 @@
 //   dvla_segment_adam_bf16 / _f32  : stage 1 for the sum of squares of r = exp_avg / denom(exp_avg_sq), denom being the step's own
 //                                    expression (adam_one / master_one of optimizer.hip); no lr enters, the host scales
 //   dvla_segment_combine           : stage 2 of either, for every segment of every bucket
+//   dvla_group_sumsq               : the per-parameter sums of squares of the gradient added per parameter group (one wave): the
+//                                    clip norms of FlatAdamW(clip="group"), instead of the dvla_sumsq_* pass
 // The host cuts every segment into chunks of DVLA_STATS_CHUNK elements counted from the segment's own first element (dvla.h: the
 // chunk table).  Stage 1: a workgroup of four waves per chunk (grid-stride over the table), 16-byte loads, thread t of the
 // workgroup owns vectors t, t + 256, ... of the chunk and adds its elements in element order; the ragged end of a segment
@@ -211,6 +213,38 @@ __global__ __launch_bounds__(256) void seg_stage2_kernel(const SegPartial* __res
   }
 }
 
+// One wave: lane g owns group g.  Every lane walks the parameters in index order (64 at a time, broadcast from the lane that
+// loaded them) and adds those of its own group, in double; a term is selected, never multiplied by a mask, so a NaN reaches
+// its own group only.  Lane 0 then adds the groups' fp32 sums in index order: step_verdict_kernel's chain over the same slots.
+__global__ __launch_bounds__(64) void group_sumsq_kernel(const float* __restrict__ param_sumsq, const uint8_t* __restrict__ group_of,
+                                                         int n_params, int n_groups, float* __restrict__ group_sumsq,
+                                                         float* __restrict__ total) {
+  static_assert(DVLA_STEP_MAX_GROUPS == 64, "one lane per group");
+  __shared__ float sums[DVLA_STEP_MAX_GROUPS];
+  const int lane = threadIdx.x;
+  double s = 0.0;
+  for (int base = 0; base < n_params; base += 64) {
+    const int rest = n_params - base;
+    const int m = rest < 64 ? rest : 64;
+    float v = 0.f;
+    int id = 255;
+    if (lane < m) { v = param_sumsq[base + lane]; id = group_of[base + lane]; }
+    for (int k = 0; k < m; ++k) {
+      const float vk = __shfl(v, k, 64);
+      if (__shfl(id, k, 64) == lane) s += (double)vk;
+    }
+  }
+  const float f = (float)s;
+  sums[lane] = f;
+  if (lane < n_groups) group_sumsq[lane] = f;
+  __syncthreads();
+  if (lane == 0 && total) {
+    float t = sums[0];
+    for (int g = 1; g < n_groups; ++g) t = t + sums[g];
+    total[0] = t;
+  }
+}
+
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <bool BF16, bool ADAM>
@@ -274,5 +308,15 @@ extern "C" int dvla_segment_combine(const void* partial, int64_t n_chunks, const
   if (!al16(partial)) return DVLA_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(seg_stage2_kernel, dim3((unsigned)((n_segs + 3) / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream_),
                      reinterpret_cast<const SegPartial*>(partial), n_chunks, segs, (int)n_segs, sumsq, absmax, nonfinite, n_out);
+  return dvla_check_launch();
+}
+
+// ---- per-group clip norms (additive, ABI 9) ---------------------------------------------------------------------------------
+extern "C" int dvla_group_sumsq(const float* param_sumsq, const uint8_t* group_of, int32_t n_params, int32_t n_groups,
+                                float* group_sumsq, float* total, void* stream_) {
+  if (!param_sumsq || !group_of || !group_sumsq || n_params < 0 || n_groups < 1 || n_groups > DVLA_STEP_MAX_GROUPS)
+    return DVLA_ERR_ARG;
+  hipLaunchKernelGGL(group_sumsq_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream_), param_sumsq, group_of,
+                     (int)n_params, (int)n_groups, group_sumsq, total);
   return dvla_check_launch();
 }

@@ -36,6 +36,11 @@ Per-parameter statistics (`parameter_stats()`, `stats_by_module`, an addition; D
 flat buffers, so `dvla_segment_stats_*` / `dvla_segment_adam_*` (one launch per bucket and buffer) and `dvla_segment_combine` (one
 launch) give per-parameter gradient and parameter norms, absmax and non-finite counts and the norm of the Adam update, with no
 atomics, no host synchronisation and no change to the step.
+
+Per-group clipping (`clip="group"`, an addition): every parameter group has its own clip norm and max_grad_norm.
+The per-parameter sums of squares of that segmented reduction, added per group by `dvla_group_sumsq`, replace the `dvla_sumsq_*`
+pass, and `dvla_adamw_*_grouped_clip` / `dvla_adamw_bf16_sr_clip` look the coefficient up per group next to lr and weight decay:
+still one launch per bucket.  `prefix_groups` cuts a model into such groups by parameter name.
 """
 import collections
 import contextlib
@@ -166,7 +171,8 @@ class FlatAdamW(torch.optim.Optimizer):
     most 64, missing keys taken from the constructor; betas and eps are common (ValueError otherwise, here and at step()).
     `self.param_groups` is the list torch's schedulers write (`LambdaLR(opt, [f0, f1])`), and step() reads every group's lr and
     weight_decay afresh.  A parameter of group g is stepped exactly -- bit for bit -- as the one-group optimizer with
-    (lr_g, weight_decay_g) steps it; the clip norm stays one norm over everything.  add_param_group raises.  Checkpoints: master
+    (lr_g, weight_decay_g) steps it; the clip norm stays one norm over everything (clip="group" below gives every group its own).
+    add_param_group raises.  Checkpoints: master
     mode keeps torch.optim.AdamW's format with several groups (a parameter's index is its position in the concatenation of the
     groups' lists, torch's numbering); the bf16-only format gains "group_params" (reducer.params indices per group).
 
@@ -182,15 +188,36 @@ class FlatAdamW(torch.optim.Optimizer):
     the grid or how a bucket is split into ranges -- so ranks that pass the same sr_seed (they must; the default does) hold the
     same weights with no communication, a skipped step draws nothing, and a run resumed from state_dict() continues bit for bit:
     the checkpoint carries the seed ("stochastic_rounding": {"seed": s}; in master-mode format inside param_groups[0]), and
-    load_state_dict() takes it over (a checkpoint without it leaves the constructor's seed)."""
+    load_state_dict() takes it over (a checkpoint without it leaves the constructor's seed).
+
+    clip="global" (the default) is everything above: one clip norm over all groups, and a "max_grad_norm" key inside a group dict
+    is carried along (state_dict() included) and not used.  clip="group" (two or more param_groups; ValueError otherwise): group
+    g's gradient is scaled by min(1, m_g / (sqrt(S_g) + 1e-6)), S_g the sum of squares over the gradients of group g's parameters
+    alone as the buckets stand after reducer.finish() -- torch's clip_grad_norm_(g["params"], m_g) -- and m_g the group's
+    "max_grad_norm": a positive float, None for a group that is not clipped, the constructor's max_grad_norm for a group without
+    the key; read afresh at every step() as lr and weight_decay are (<= 0 or not finite: ValueError at step()).  A parameter of
+    group g is stepped bit for bit as the one-group optimizer with (lr_g, weight_decay_g, m_g) steps it on a gradient whose sum
+    of squares is S_g, and depends on no other group's gradient: unguarded, a NaN in one group's gradient stays in that group (its
+    norm is NaN, its coefficient therefore 1 as in the one-group kernels, the elements it sits in become NaN) and leaves every
+    other group's bits alone.  Works with skip_nonfinite, ema_decay and stochastic_rounding in any combination, at
+    one step launch per bucket.  The guard still takes ONE verdict per step, on the sum of the groups' sums in group order: a
+    non-finite group skips the step for every group; health() then reports "skipped_group_norms" and the first-skip warning names
+    the group(s).  As with the global clip, a scheduler that rewrites lr or max_grad_norm on the host advances on skipped steps.
+    grad_norm() stays the global norm; group_grad_norms() / group_grad_sumsq() give the groups' (device tensors, no
+    synchronisation; RuntimeError under clip="global").  A group's norm is built from per-parameter sums and does not depend on
+    bucket_bytes; its relative error is parameter_stats()' plus one fp32 rounding.  `clip` is a constructor property and is not
+    stored; every group's "max_grad_norm" round-trips through state_dict() in both formats, and a checkpoint without the key
+    leaves the groups as constructed."""
 
     WINDOW = 8     # guarded steps in flight before step() waits for the oldest readback
 
     def __init__(self, reducer, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, amsgrad=False,
                  maximize=False, skip_nonfinite=False, ema_decay=None, ema_warmup=False, param_groups=None, stochastic_rounding=False,
-                 sr_seed=0):
+                 sr_seed=0, clip="global"):
         if amsgrad or maximize:
             raise ValueError("FlatAdamW: amsgrad and maximize are not supported")
+        param_groups = None if param_groups is None else list(param_groups)
+        self.clip = resolve_clip(clip, 1 if param_groups is None else len(param_groups))
         if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
             raise ValueError(f"FlatAdamW: ema_decay must lie strictly between 0 and 1 ({ema_decay!r} given)")
         self.stochastic_rounding = bool(stochastic_rounding)
@@ -240,6 +267,10 @@ class FlatAdamW(torch.optim.Optimizer):
         dev = reducer.buckets[0]["flat"].device
         self._sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
         self._partial = torch.empty(int(lib.dvla_sumsq_partial_len()), dtype=torch.float32, device=dev)
+        if self.clip == "group":            # per parameter and per group: the sums of squares of the last step's gradient
+            self._param_sumsq = torch.zeros(len(reducer.params), dtype=torch.float32, device=dev)
+            self._group_sumsq = torch.zeros(len(self.param_groups), dtype=torch.float32, device=dev)
+            self._group_ids = torch.tensor([self._group_of[id(p)] for p in reducer.params], dtype=torch.uint8).to(dev)
         if self.skip_nonfinite:
             self._slots = torch.zeros(len(self.flat), dtype=torch.float32, device=dev)         # one sum of squares per bucket
             self._state = torch.zeros(ctypes.sizeof(_lib.StepState), dtype=torch.uint8, device=dev)      # dvla_step_state
@@ -281,15 +312,18 @@ class FlatAdamW(torch.optim.Optimizer):
             return [False] * len(b["params"])
         return b["expected"]
 
-    def _sr_launch(self, lib, bi, lo, hi, gmap, lrs, wds, b1, b2, eps, step, sumsq, max_norm, state, ema_w, n_cand, stream):
+    def _sr_launch(self, lib, bi, lo, hi, gmap, lrs, wds, b1, b2, eps, step, sumsq, max_norm, state, ema_w, n_cand, stream,
+                   per_group=False):
         """elements lo .. hi of bf16 bucket bi through dvla_adamw_bf16_sr: the plain / guarded / EMA / grouped step of a bf16
-        bucket (gmap None: one group) with stochastically rounded stores; the element index of the random bits starts at lo"""
+        bucket (gmap None: one group) with stochastically rounded stores; the element index of the random bits starts at lo.
+        per_group: through dvla_adamw_bf16_sr_clip, sumsq the groups' sums on the device and max_norm the host array"""
         s = self.flat[bi]
         o = 2 * lo
-        check(lib.dvla_adamw_bf16_sr(s["p"].data_ptr() + o, s["g"].data_ptr() + o, s["m"].data_ptr() + o, s["v"].data_ptr() + o,
-                                     s["ema"].data_ptr() + 4 * lo if ema_w is not None else None, hi - lo, gmap, len(lrs), lrs, wds,
-                                     float(b1), float(b2), eps, step, sumsq, max_norm, state, ema_w, n_cand, self.sr_seed, bi, lo,
-                                     stream), "dvla_adamw_bf16_sr")
+        fn = lib.dvla_adamw_bf16_sr_clip if per_group else lib.dvla_adamw_bf16_sr
+        check(fn(s["p"].data_ptr() + o, s["g"].data_ptr() + o, s["m"].data_ptr() + o, s["v"].data_ptr() + o,
+                 s["ema"].data_ptr() + 4 * lo if ema_w is not None else None, hi - lo, gmap, len(lrs), lrs, wds,
+                 float(b1), float(b2), eps, step, sumsq, max_norm, state, ema_w, n_cand, self.sr_seed, bi, lo,
+                 stream), "dvla_adamw_bf16_sr")
 
     @torch.no_grad()
     def _guarded_step(self):
@@ -360,11 +394,18 @@ class FlatAdamW(torch.optim.Optimizer):
         # together (the step just confirmed may be an earlier one)
         tail = self._state.cpu()
         last = int(tail[_lib.StepState.latched_step.offset:][:8].view(torch.int64)[0])
-        sums = tail[_lib.StepState.skipped_bucket_sumsq.offset:][:4 * len(self.flat)].view(torch.float32).tolist()
+        n_slots = len(self.param_groups) if self.clip == "group" else len(self.flat)      # what the verdict was fed
+        sums = tail[_lib.StepState.skipped_bucket_sumsq.offset:][:4 * n_slots].view(torch.float32).tolist()
         bad = [i for i, x in enumerate(sums) if not math.isfinite(x)]
-        where = f"non-finite gradient in bucket(s) {bad}" if bad else "the gradient norm overflows fp32"
         first = "" if last == step else f" (the first confirmed skip was step {step})"
-        warnings.warn(f"FlatAdamW: step {last} was skipped: {where}{first}; see bucket_parameters().  Further skips are counted "
+        if self.clip == "group":
+            named = [f"{i} ({self.param_groups[i]['name']!r})" if "name" in self.param_groups[i] else str(i) for i in bad]
+            where = f"non-finite gradient in parameter group(s) {', '.join(named)}" if bad else "the gradient norm overflows fp32"
+            see = 'parameter_stats("grad")["grad_nonfinite"] names the parameter(s)'
+        else:
+            where = f"non-finite gradient in bucket(s) {bad}" if bad else "the gradient norm overflows fp32"
+            see = "see bucket_parameters()"
+        warnings.warn(f"FlatAdamW: step {last} was skipped: {where}{first}; {see}.  Further skips are counted "
                       f"in health() / skipped_steps without a warning.", RuntimeWarning, stacklevel=3)
 
     def _state_view(self, field, dtype):
@@ -378,14 +419,20 @@ class FlatAdamW(torch.optim.Optimizer):
     def health(self):
         """the guard's account as device tensors (copies enqueued on the current stream, no synchronisation): steps applied and
         skipped, the last step's verdict (1 applied / 0 skipped) and gradient norm, and the 1-based number and per-bucket gradient
-        norms of the last skipped step (bucket_parameters(i) says what lives in bucket i)"""
+        norms of the last skipped step (bucket_parameters(i) says what lives in bucket i).  With clip="group" the verdict is taken
+        over the groups' sums, and "skipped_group_norms" (one per parameter group) stands in place of "skipped_bucket_norms"."""
         self._require_guard("health()")
-        return {"applied": self._state_view("applied", torch.int64)[0].clone(),
-                "skipped": self._state_view("skipped", torch.int64)[0].clone(),
-                "last_ok": self._state_view("ok", torch.int32)[0].clone(),
-                "last_grad_norm": self._state_view("sumsq", torch.float32)[0].sqrt(),
-                "last_skipped_step": self._state_view("latched_step", torch.int64)[0].clone(),
-                "skipped_bucket_norms": self._state_view("skipped_bucket_sumsq", torch.float32)[:len(self.flat)].sqrt()}
+        out = {"applied": self._state_view("applied", torch.int64)[0].clone(),
+               "skipped": self._state_view("skipped", torch.int64)[0].clone(),
+               "last_ok": self._state_view("ok", torch.int32)[0].clone(),
+               "last_grad_norm": self._state_view("sumsq", torch.float32)[0].sqrt(),
+               "last_skipped_step": self._state_view("latched_step", torch.int64)[0].clone()}
+        latched = self._state_view("skipped_bucket_sumsq", torch.float32)
+        if self.clip == "group":
+            out["skipped_group_norms"] = latched[:len(self.param_groups)].sqrt()
+        else:
+            out["skipped_bucket_norms"] = latched[:len(self.flat)].sqrt()
+        return out
 
     def bucket_parameters(self, i):
         """indices into reducer.params of the parameters in gradient bucket i"""
@@ -500,7 +547,9 @@ class FlatAdamW(torch.optim.Optimizer):
 
     def _grouped_step(self):
         """step() with two or more parameter groups: one dvla_adamw_*_grouped launch per bucket, guarded or not, with or without
-        the EMA; every group's lr / weight_decay is read afresh.  One clip norm over all buckets and groups."""
+        the EMA; every group's lr / weight_decay is read afresh.  One clip norm over all buckets and groups -- with clip="group"
+        one per group (_group_norms instead of the dvla_sumsq_* pass, the `_clip` entry points instead of the grouped ones), every
+        group's max_grad_norm read afresh as well."""
         lib = _lib.load()
         stream = torch.cuda.current_stream().cuda_stream
         b1, b2, eps = common_betas_eps(self.param_groups)
@@ -509,42 +558,57 @@ class FlatAdamW(torch.optim.Optimizer):
         wds = (ctypes.c_double * n_groups)(*[float(g["weight_decay"]) for g in self.param_groups])
         guard, ema, clip = self.skip_nonfinite, self.ema_decay is not None, self.max_grad_norm is not None
         max_norm = self.max_grad_norm if clip else 0.0      # guarded, <= 0: the norm only feeds the verdict
+        per_group = self.clip == "group"
+        if per_group:   # (0: the group is not clipped; its norm still feeds the verdict and group_grad_norms())
+            max_norm = (ctypes.c_float * n_groups)(*[0.0 if m is None else m
+                                                     for m in group_max_norms(self.param_groups, self.max_grad_norm)])
         if guard:       # the verdict as in _guarded_step; of its candidates the grouped kernels use what no lr enters
             confirmed, n_cand = self._ledger.begin()
             self.step_count = confirmed
             base, state, sumsq = confirmed + 1, self._state.data_ptr(), None
-            for i, s in enumerate(self.flat):
-                fn = lib.dvla_sumsq_f32 if "sh" in s else lib.dvla_sumsq_bf16
-                check(fn(s["g"].data_ptr(), s["g"].numel(), self._partial.data_ptr(), self._slots.data_ptr() + 4 * i, 0, stream),
-                      "dvla_sumsq")
+            if per_group:       # the groups' sums are the verdict's slots: their total in group order, latched per group on a skip
+                self._group_norms(lib, stream, None)
+                slots, n_slots = self._group_sumsq, n_groups
+            else:
+                for i, s in enumerate(self.flat):
+                    fn = lib.dvla_sumsq_f32 if "sh" in s else lib.dvla_sumsq_bf16
+                    check(fn(s["g"].data_ptr(), s["g"].numel(), self._partial.data_ptr(), self._slots.data_ptr() + 4 * i, 0, stream),
+                          "dvla_sumsq")
+                slots, n_slots = self._slots, len(self.flat)
             check(lib.dvla_step_candidates(lrs[0], b1, b2, base, n_cand, self._cand), "dvla_step_candidates")
-            check(lib.dvla_step_verdict(self._slots.data_ptr(), len(self.flat), self._sumsq.data_ptr(), state, confirmed, n_cand,
+            check(lib.dvla_step_verdict(slots.data_ptr(), n_slots, self._sumsq.data_ptr(), state, confirmed, n_cand,
                                         self._cand, stream), "dvla_step_verdict")
         else:
             self.step_count += 1
             base, n_cand, state, sumsq = self.step_count, 1, None, (self._sumsq.data_ptr() if clip else None)
-            if clip:
+            if per_group:
+                self._group_norms(lib, stream, self._sumsq.data_ptr())
+            elif clip:
                 for i, s in enumerate(self.flat):
                     fn = lib.dvla_sumsq_f32 if "sh" in s else lib.dvla_sumsq_bf16
                     check(fn(s["g"].data_ptr(), s["g"].numel(), self._partial.data_ptr(), self._sumsq.data_ptr(), 1 if i > 0 else 0,
                              stream), "dvla_sumsq")
+        if per_group:
+            sumsq = self._group_sumsq.data_ptr()
         if ema:
             check(lib.dvla_ema_weights(self.ema_decay, int(self.ema_warmup), base, n_cand, self._ema_w), "dvla_ema_weights")
         ema_w = self._ema_w if ema else None
+        master_fn = lib.dvla_adamw_f32_master_grouped_clip if per_group else lib.dvla_adamw_f32_master_grouped
+        bf16_fn = lib.dvla_adamw_bf16_grouped_clip if per_group else lib.dvla_adamw_bf16_grouped
         for bi, s in enumerate(self.flat):
             if not any(self._stepped(bi)):
                 continue
             e = s["ema"].data_ptr() if ema else None
             if "sh" in s:
-                check(lib.dvla_adamw_f32_master_grouped(
+                check(master_fn(
                     s["p"].data_ptr(), s["g"].data_ptr(), s["m"].data_ptr(), s["v"].data_ptr(), s["sh"].data_ptr(), e,
                     s["p"].numel(), self._group_map(bi).data_ptr(), n_groups, lrs, wds, b1, b2, eps, base, sumsq, max_norm, state,
                     ema_w, n_cand, stream), "dvla_adamw_f32_master_grouped")
             elif self.stochastic_rounding:
                 self._sr_launch(lib, bi, 0, s["p"].numel(), self._group_map(bi).data_ptr(), lrs, wds, b1, b2, eps, base, sumsq,
-                                max_norm, state, ema_w, n_cand, stream)
+                                max_norm, state, ema_w, n_cand, stream, per_group=per_group)
             else:
-                check(lib.dvla_adamw_bf16_grouped(
+                check(bf16_fn(
                     s["p"].data_ptr(), s["g"].data_ptr(), s["m"].data_ptr(), s["v"].data_ptr(), e, s["p"].numel(),
                     self._group_map(bi).data_ptr(), n_groups, lrs, wds, b1, b2, eps, base, sumsq, max_norm, state, ema_w, n_cand,
                     stream), "dvla_adamw_bf16_grouped")
@@ -589,8 +653,42 @@ class FlatAdamW(torch.optim.Optimizer):
         self.reducer.zero_grad()
 
     def grad_norm(self):
-        """total gradient norm of the last step() with clipping (device scalar tensor)"""
+        """total gradient norm of the last step() with clipping (device scalar tensor); with clip="group" the root of the groups'
+        sums of squares added in group order"""
         return self._sumsq.sqrt()
+
+    def _group_norms(self, lib, stream, total):
+        """clip="group": every group's sum of squares of the gradient buckets as they stand into self._group_sumsq -- stage 1 of
+        the segmented reduction per bucket and its combine over parameter_stats()' tables (per parameter, so a group's sum does not
+        depend on the bucket layout), then dvla_group_sumsq; `total` (a device address or None) receives their sum"""
+        tabs, n_records, segs, scratch = self._stats_tables()
+        n = len(self.reducer.params)
+        for s, (chunks, n_chunks, first) in zip(self.flat, tabs):
+            if n_chunks:
+                fn = lib.dvla_segment_stats_f32 if s["g"].dtype == torch.float32 else lib.dvla_segment_stats_bf16
+                check(fn(s["g"].data_ptr(), s["g"].numel(), chunks.data_ptr(), n_chunks,
+                         scratch.data_ptr() + first * _lib.STATS_PARTIAL_BYTES, stream), "dvla_segment_stats")
+        check(lib.dvla_segment_combine(scratch.data_ptr(), n_records, segs.data_ptr(), n, self._param_sumsq.data_ptr(), None, None, n,
+                                       stream), "dvla_segment_combine")
+        check(lib.dvla_group_sumsq(self._param_sumsq.data_ptr(), self._group_ids.data_ptr(), n, len(self.param_groups),
+                                   self._group_sumsq.data_ptr(), total, stream), "dvla_group_sumsq")
+
+    def _require_group_clip(self, what):
+        if self.clip != "group":
+            raise RuntimeError(f'FlatAdamW.{what}: construct the optimizer with clip="group" (with clip="global" there is one norm: '
+                               f'grad_norm())')
+
+    def group_grad_sumsq(self):
+        """clip="group": the sum of squares of every parameter group's gradient at the last step(), before clipping, groups that
+        are not clipped included -> (n_groups,) fp32 device tensor (a copy; no host synchronisation)"""
+        self._require_group_clip("group_grad_sumsq()")
+        return self._group_sumsq.clone()
+
+    def group_grad_norms(self):
+        """clip="group": the gradient norm of every parameter group at the last step(), before clipping -- what each group's
+        max_grad_norm is held against -> (n_groups,) fp32 device tensor (no host synchronisation)"""
+        self._require_group_clip("group_grad_norms()")
+        return self._group_sumsq.sqrt()
 
     # ---- per-parameter statistics (parameter_stats) ----------------------------------------------------------------------------
     def _stats_tables(self):
@@ -863,6 +961,8 @@ class FlatAdamW(torch.optim.Optimizer):
             for mine, saved in zip(self.param_groups, groups):
                 for k in ("lr", "betas", "eps", "weight_decay"):
                     mine[k] = saved[k]
+                if "max_grad_norm" in saved:        # (a checkpoint without it keeps what the group has)
+                    mine["max_grad_norm"] = saved["max_grad_norm"]
             return
         layout = [[int(p.numel()) for p in b["params"]] for b in self.reducer.buckets]
         if sd["layout"] != layout:
@@ -939,6 +1039,85 @@ def common_betas_eps(groups):
             raise ValueError(f"FlatAdamW: group {gi} has betas = {g['betas']!r}, eps = {g['eps']!r}, group 0 {groups[0]['betas']!r}, "
                              f"{groups[0]['eps']!r}: betas and eps are common to all groups")
     return betas[0], betas[1], eps
+
+
+def resolve_clip(clip, n_groups):
+    """FlatAdamW's `clip` checked against the number of parameter groups (pure): "global" or "group"; "group" needs two groups"""
+    if clip not in ("global", "group"):
+        raise ValueError(f'FlatAdamW: clip must be "global" or "group" ({clip!r} given)')
+    if clip == "group" and n_groups < 2:
+        raise ValueError(f'FlatAdamW(clip="group"): {n_groups} parameter group given; with fewer than two groups this would be the '
+                         f'global clip -- pass param_groups=[...] with two or more groups, or clip="global"')
+    return clip
+
+
+def group_max_norms(groups, default):
+    """every group's clip value for FlatAdamW(clip="group") (pure): the group's "max_grad_norm" -- a positive finite float, or
+    None: the group is not clipped --, `default` (the constructor's max_grad_norm) for a group without the key.  ValueError names
+    the group of a value that is <= 0, not finite or not a number."""
+    out = []
+    for gi, g in enumerate(groups):
+        m = g.get("max_grad_norm", default)
+        if m is not None:
+            try:
+                m = None if isinstance(m, bool) else float(m)
+            except (TypeError, ValueError):
+                m = None
+            if m is None or not (m > 0.0 and math.isfinite(m)):
+                raise ValueError(f"FlatAdamW: group {gi} has max_grad_norm = {g.get('max_grad_norm', default)!r}: a positive finite "
+                                 f"number, or None for a group that is not clipped")
+        out.append(m)
+    return out
+
+
+def prefix_groups(model_or_named_parameters, prefixes, rest="rest", **per_group):
+    """Parameter groups cut by parameter name (pure), as plain torch groups that also carry "name":
+    prefixes = {"heads": ("image_decoder", "action_head."), "trunk": ("transformer.",)} puts a trainable parameter into the group
+    one of whose prefixes its name starts with (str.startswith; the longest matching prefix decides between groups), everything
+    else into the group named `rest` (rest=None: an unmatched parameter is a ValueError).  Frozen parameters are left out and a
+    parameter shared under two names counts once, under its first.  Every keyword is a group key given per group name,
+    max_grad_norm={"heads": 0.05, "trunk": None}, lr={"trunk": 1e-4}: a group that is not named does not get the key (FlatAdamW
+    fills in its constructor's value).  Groups come in the order of `prefixes`, `rest` last (omitted if empty), parameters in
+    the order of named_parameters().  ValueError names a prefix that matches nothing, a prefix given to two groups and a group name
+    no group has."""
+    named = model_or_named_parameters
+    named = named.named_parameters() if hasattr(named, "named_parameters") else named
+    owner = {}
+    for name, pres in prefixes.items():
+        for pre in ((pres,) if isinstance(pres, str) else tuple(pres)):
+            if pre in owner:
+                raise ValueError(f"prefix_groups: the prefix {pre!r} is given to two groups ({owner[pre]!r} and {name!r})")
+            owner[pre] = name
+    if rest is not None and rest in prefixes:
+        raise ValueError(f"prefix_groups: {rest!r} is the name of the group of everything else and of a group of `prefixes`")
+    params = {name: [] for name in prefixes}
+    if rest is not None:
+        params[rest] = []
+    hit, seen = set(), set()
+    for pname, p in named:
+        if not p.requires_grad or id(p) in seen:
+            continue
+        seen.add(id(p))
+        match = max((pre for pre in owner if pname.startswith(pre)), key=len, default=None)
+        if match is None and rest is None:
+            raise ValueError(f"prefix_groups: the parameter {pname!r} matches no prefix and there is no `rest` group")
+        hit.add(match)
+        params[rest if match is None else owner[match]].append(p)
+    for pre in owner:
+        if pre not in hit:
+            raise ValueError(f"prefix_groups: the prefix {pre!r} (group {owner[pre]!r}) matches no trainable parameter")
+    for key, values in per_group.items():
+        for name in values:
+            if name not in params:
+                raise ValueError(f"prefix_groups: {key} names the group {name!r}; the groups are {', '.join(map(repr, params))}")
+    groups = []
+    for name, ps in params.items():
+        if name == rest and not ps:
+            continue
+        g = {"name": name, "params": ps}
+        g.update({key: values[name] for key, values in per_group.items() if name in values})
+        groups.append(g)
+    return groups
 
 
 def build_group_map(offsets, sizes, total, group_ids, stepped, n_groups):
@@ -1044,6 +1223,8 @@ def _torch_group(g, n, start=0):
     out = {"lr": g["lr"], "betas": tuple(g["betas"]), "eps": g["eps"], "weight_decay": g["weight_decay"], "amsgrad": False,
            "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
            "decoupled_weight_decay": True}
+    if "max_grad_norm" in g:        # a group's own clip value (FlatAdamW(clip="group")); torch carries extra keys along
+        out["max_grad_norm"] = g["max_grad_norm"]
     out["params"] = list(range(start, start + n))
     return out
 

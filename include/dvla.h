@@ -591,6 +591,46 @@ int dvla_segment_adam_f32(const float* exp_avg, const float* exp_avg_sq, int64_t
                           void* partial, double beta2, double eps, int64_t step, void* stream);
 int dvla_segment_combine(const void* partial, int64_t n_chunks, const int64_t* segs, int32_t n_segs, float* sumsq, float* absmax,
                          int64_t* nonfinite, int64_t n_out, void* stream);
+/* (additive, ABI 9) Per-group gradient clipping: every parameter group has its own clip norm and its own
+ * max_norm, inside the one launch per bucket of the grouped step.  A parameter of group g comes out bit-identical to that
+ * parameter under the one-group entry points called with (lr[g], weight_decay[g]), grad_sumsq = &group_sumsq[g] and
+ * max_norm[g] -- grad_sumsq = NULL for a group that is not clipped --, and depends on no other group's gradient.
+ * dvla_group_sumsq: one launch of one wave, behind dvla_segment_stats_* over the gradient buckets and dvla_segment_combine.
+ *   param_sumsq[i], i < n_params, is parameter i's sum of squares and group_of[i] its group (one byte; an id >= n_groups: the
+ *   parameter is in no sum).  group_sumsq[g], g < n_groups, = the sum of the group's parameters in index order, accumulated in
+ *   double and rounded to fp32 once (a non-finite term reaches its own group only: nothing is multiplied by a mask); a group
+ *   without parameters gets 0.  total (may be NULL) receives group_sumsq[0] + group_sumsq[1] + ... added in fp32 in index
+ *   order, the chain of dvla_step_verdict over the same slots, so the guarded and the unguarded step see the same total.  No
+ *   atomics, and two calls give the same bits; with per-parameter terms from the segmented reduction the result does not
+ *   depend on how the parameters are laid out in buckets.
+ *   DVLA_ERR_ARG: a null pointer (total excepted), n_params < 0, n_groups outside 1 .. DVLA_STEP_MAX_GROUPS.
+ * dvla_adamw_bf16_grouped_clip / dvla_adamw_f32_master_grouped_clip / dvla_adamw_bf16_sr_clip: dvla_adamw_bf16_grouped /
+ *   dvla_adamw_f32_master_grouped / dvla_adamw_bf16_sr with the clip coefficient per group instead of per launch:
+ *   group_sumsq: device memory, n_groups floats (dvla_group_sumsq's), read by the kernel -- no host synchronisation;
+ *   max_norm:    a HOST array of n_groups floats, copied into the kernel arguments; max_norm[g] > 0: group g's gradient is
+ *                scaled by min(1, max_norm[g] / (sqrt(group_sumsq[g]) + 1e-6)), the one-group kernels' expression; anything
+ *                else (<= 0, NaN): group g is not clipped and group_sumsq[g] is not read.
+ *   state != NULL: the guarded step; the verdict is dvla_step_verdict's over the group sums (one verdict per step, not per
+ *   group) and state->sumsq is not used for clipping.  dvla_adamw_bf16_sr_clip needs a group_map (the one-group step has one
+ *   clip norm: dvla_adamw_bf16_sr).
+ *   Errors as the entry point without `_clip`, + DVLA_ERR_ARG for group_sumsq == NULL, max_norm == NULL and, for
+ *   dvla_adamw_bf16_sr_clip, group_map == NULL.  All of these return before anything touches the device. */
+int dvla_group_sumsq(const float* param_sumsq, const uint8_t* group_of, int32_t n_params, int32_t n_groups, float* group_sumsq,
+                     float* total, void* stream);
+int dvla_adamw_bf16_grouped_clip(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, float* ema, int64_t n,
+                                 const uint8_t* group_map, int32_t n_groups, const double* lr, const double* weight_decay,
+                                 float beta1, float beta2, float eps, int64_t step, const float* group_sumsq, const float* max_norm,
+                                 const dvla_step_state* state, const float* ema_w, int32_t n_cand, void* stream);
+int dvla_adamw_f32_master_grouped_clip(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
+                                       float* ema, int64_t n, const uint8_t* group_map, int32_t n_groups, const double* lr,
+                                       const double* weight_decay, double beta1, double beta2, double eps, int64_t step,
+                                       const float* group_sumsq, const float* max_norm, const dvla_step_state* state,
+                                       const float* ema_w, int32_t n_cand, void* stream);
+int dvla_adamw_bf16_sr_clip(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, float* ema, int64_t n,
+                            const uint8_t* group_map, int32_t n_groups, const double* lr, const double* weight_decay, float beta1,
+                            float beta2, float eps, int64_t step, const float* group_sumsq, const float* max_norm,
+                            const dvla_step_state* state, const float* ema_w, int32_t n_cand, uint64_t sr_seed, int32_t sr_bucket,
+                            int64_t sr_index_base, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Token assembly (models/dreamvla_model.py:739-759): out[b, s, t, :] = part_k[b, s, t - tok_begin_k, :] + pos[s, :]
