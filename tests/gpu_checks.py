@@ -1244,6 +1244,121 @@ def check_attention_masked(case):
     return out, struct
 
 
+def check_attention_values(case):
+    """HIP attention on one value regime (a case of tests/attention_value_ref.py: one-hot rows, sinks, staircases of the running
+    maximum, mixed temperatures in one wave, outlier channels, tiny / big magnitudes, huge logits behind the mask, ties, exact
+    integers) against the float64 reference of that module.  Forward: o and lse.  Backward: the kernels' dq, dk, dv, run on their
+    own o and lse exactly as the product does, against the float64 backward CONDITIONED on the o the kernel stored.  Per tensor
+    tol = max(suite tolerance, 4 E), k_ulp = max(suite k, 4 U) with E, U the yardstick of the case (what correct float32 restatements
+    differ from the reference by; capped on the CPU at 1e-2 / 16 ulps).  Exact, no tolerance: everything written is finite, a query
+    that sees no key has o = 0, lse = +inf, dq = 0, and the `exact` family's o and dv equal the float64 result bit for bit.
+    via "raw": ops.attn_fwd_raw / attn_bwd_raw on strided views of packed buffers, gradients into NaN-pre-filled views;
+    via "self" / "cross": the autograd wrappers (o is the returned tensor; they do not return lse).
+    -> (list of metric dicts, yardstick)"""
+    from dreamvla_amd import ops
+    from tests import attention_value_ref as V
+    B, H, Lq, Lk, D, p_drop = case["B"], case["H"], case["Lq"], case["Lk"], case["D"], case["p"]
+    data, yard = V.yardstick(case)
+    vis = data["vis"]
+    mt = V.tables(case, vis, device=DEV)
+    scale = D ** -0.5
+    tok = lambda t: t.permute(0, 2, 1, 3)                                   # (B, H, L, D) <-> (B, L, H, D)
+    host = lambda t: tok(t.detach().float().cpu())
+    W = H * D
+    tag = "attn_values " + case["id"]
+    got = {}
+    if case["via"] == "self":
+        assert Lq == Lk and p_drop == 0
+        qkv = torch.stack((tok(data["q"]), tok(data["k"]), tok(data["v"])), dim=2).reshape(B, Lq, 3 * W).to(DEV, BF).requires_grad_(True)
+        o = ops.self_attention(qkv, H, mask_tables=mt, head_dim=D)
+        o.backward(tok(data["dout"]).reshape(B, Lq, W).to(DEV, BF))
+        g5 = qkv.grad.view(B, Lq, 3, H, D)
+        got = {"o": host(o.view(B, Lq, H, D)), "dq": host(g5[:, :, 0]), "dk": host(g5[:, :, 1]), "dv": host(g5[:, :, 2])}
+    elif case["via"] == "cross":
+        assert mt is None and p_drop == 0 and D == 64
+        qd = tok(data["q"]).reshape(B, Lq, W).to(DEV, BF).requires_grad_(True)
+        kvd = torch.stack((tok(data["k"]), tok(data["v"])), dim=2).reshape(B, Lk, 2 * W).to(DEV, BF).requires_grad_(True)
+        o = ops.cross_attention(qd, kvd, H)
+        o.backward(tok(data["dout"]).reshape(B, Lq, W).to(DEV, BF))
+        g5 = kvd.grad.view(B, Lk, 2, H, D)
+        got = {"o": host(o.view(B, Lq, H, D)), "dq": host(qd.grad.view(B, Lq, H, D)), "dk": host(g5[:, :, 0]), "dv": host(g5[:, :, 1])}
+    else:
+        if Lq == Lk:
+            buf = torch.stack((tok(data["q"]), tok(data["k"]), tok(data["v"])), dim=2).contiguous().to(DEV, BF)      # (B, L, 3, H, D)
+            gbuf = torch.full_like(buf, float("nan"))
+            (q, k, v), (dq, dk, dv) = buf.unbind(2), gbuf.unbind(2)
+        else:
+            q = tok(data["q"]).contiguous().to(DEV, BF)
+            kv = torch.stack((tok(data["k"]), tok(data["v"])), dim=2).contiguous().to(DEV, BF)
+            dq, gkv = torch.full_like(q, float("nan")), torch.full_like(kv, float("nan"))
+            (k, v), (dk, dv) = kv.unbind(2), gkv.unbind(2)
+        kw = dict(scale=scale, mask_tables=mt, dropout_p=p_drop, seed=V.drop_of(case)[1] if p_drop > 0 else (0, 0), head_dim=D)
+        o, lse = ops.attn_fwd_raw(q, k, v, **kw)
+        ops.attn_bwd_raw(q, k, v, o, lse, tok(data["dout"]).contiguous().to(DEV, BF), dq, dk, dv, **kw)
+        torch.cuda.synchronize()
+        got = {"o": host(o), "lse": lse.detach().float().cpu(), "dq": host(dq), "dk": host(dk), "dv": host(dv)}
+    named = None
+    if mt is not None and mt.key_index is not None:
+        named = torch.zeros(Lk, dtype=torch.bool)
+        named[mt.key_index.cpu().long()] = True
+    out = V.judge(case, data, yard, got, tag=tag, named=named)
+    # exact: finiteness of everything written, the convention for a query that sees no key
+    rows_k = slice(None) if named is None else named
+    finite = all(bool(torch.isfinite(got[n]).all()) for n in ("o", "dq")) and all(bool(torch.isfinite(got[n][:, :, rows_k]).all()) for n in ("dk", "dv"))
+    blind = torch.zeros(Lq, dtype=torch.bool) if vis is None else torch.from_numpy(~vis.any(axis=1))
+    if "lse" in got:
+        finite = finite and bool(torch.isfinite(got["lse"][..., ~blind]).all())
+        out.append(_exact(tag + f": lse of the {int(blind.sum())} blind queries is +inf", (got["lse"][..., blind] == float("inf")).all()))
+    out.append(_exact(tag + ": everything written is finite", finite))
+    zero = lambda t: bool((t == 0).all())
+    out.append(_exact(tag + ": o and dq of blind queries are 0", zero(got["o"][:, :, blind]) and zero(got["dq"][:, :, blind])))
+    return out, yard
+
+
+def check_attention_probe_values(regime, mask, compact, L=133, D=64, B=2, H=2, R_rows=32):
+    """ops.attention_probe on a value regime of tests/attention_value_ref.py against the float64 softmax of
+    tests/attention_probe_ref.py, by the derived bound tests/test_attention_probe_gpu.py uses.  On top of it one absolute term: a
+    probability below 2^-126 has no normal fp32 representation (the kernel may flush it to 0), so 2^-126 is added to the bound.
+    Exact: a key the row cannot see, a blind row hold 0.0; every element is written (NaN pre-fill) and finite."""
+    import numpy as np
+    from dreamvla_amd import ops
+    from tests import attention_probe_ref as PR
+    from tests import attention_value_ref as V
+    case = V._case("probe", regime, L, D=D, B=B, H=H, mask=mask, compact=compact)
+    data = V.values(case)
+    vis = data["vis"]
+    mt = V.tables(case, vis, device=DEV)
+    tok = lambda t: t.permute(0, 2, 1, 3).contiguous()
+    q, k = tok(data["q"]).to(DEV, BF), tok(data["k"]).to(DEV, BF)
+    rng = np.random.default_rng(5)
+    rows = np.stack([rng.permutation(L)[:R_rows] for _ in range(B)]).astype(np.int32)
+    rows[0, 0], rows[B - 1, 1] = 0, L - 1
+    if vis is not None:
+        rows[0, 2] = int(np.nonzero(~vis.any(axis=1))[0][0])              # a blind row
+    scale = D ** -0.5
+    tag = f"probe values {regime} mask={mask}" + ("" if compact else " uncompacted")
+    res = []
+    for per_head in (True, False):
+        shape = (B, H, R_rows, L) if per_head else (B, R_rows, L)
+        out = torch.full(shape, float("nan"), device=DEV)
+        ops.attention_probe(q, k, torch.from_numpy(rows).to(DEV), scale=scale, mask_tables=mt, per_head=per_head, out=out)
+        torch.cuda.synchronize()
+        g = out.double().cpu().numpy()
+        ref = PR.probabilities(tok(data["q"]).numpy(), tok(data["k"]).numpy(), rows, scale, vis)
+        want = ref["per_head" if per_head else "mean"]
+        bnd = PR.bound(ref, D, L if mt is None else mt.Lk, per_head) + 2.0 ** -126
+        err = np.abs(g - want)
+        finite = bool(np.isfinite(g).all())
+        zeros = bool((g[want == 0.0] == 0.0).all())
+        live = want > 0
+        ratio = float((err[live] / bnd[live]).max()) if finite and live.any() else float("inf")
+        res.append({"name": tag + (" per head" if per_head else " head mean"), "worst_err_over_bound": ratio, "max_abs_err": float(np.nanmax(err)),
+                    "top_probability_median": float(np.median(ref["per_head"].max(axis=-1)[ref["per_head"].max(axis=-1) > 0])),
+                    "rel_l2": float(np.linalg.norm(np.nan_to_num(g - want)) / max(np.linalg.norm(want), 1e-300)), "tol": 1.0,
+                    "ok": bool(finite and zeros and ratio <= 1.0)})
+    return res
+
+
 def check_self_attention_uncompacted(case, runs=2):
     """_SelfAttention.backward allocates its gradient with torch.empty_like and, under tables without a key_index (compact_keys =
     False), zero-fills nothing: the dK/dV kernels must write every row themselves, dead keys' rows included.  ops.self_attention +
