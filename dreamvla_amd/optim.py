@@ -47,15 +47,13 @@ import contextlib
 import ctypes
 import math
 import operator
+import types
 import warnings
 
 import torch
 
 from . import _lib, ops
 from ._lib import check
-
-
-_ONE_DOUBLE = ctypes.c_double * 1      # the one-group (lr, weight_decay) as dvla_adamw_bf16_sr takes them
 
 
 class _StepLedger:
@@ -325,66 +323,13 @@ class FlatAdamW(torch.optim.Optimizer):
                  float(b1), float(b2), eps, step, sumsq, max_norm, state, ema_w, n_cand, self.sr_seed, bi, lo,
                  stream), "dvla_adamw_bf16_sr")
 
-    @torch.no_grad()
-    def _guarded_step(self):
-        lib = _lib.load()
-        stream = torch.cuda.current_stream().cuda_stream
-        grp = self.param_groups[0]
-        lr, (b1, b2), eps, wd = float(grp["lr"]), grp["betas"], float(grp["eps"]), float(grp["weight_decay"])
-        max_norm = self.max_grad_norm if self.max_grad_norm is not None else 0.0        # <= 0: the norm only feeds the verdict
-        confirmed, n_cand = self._ledger.begin()
-        self.step_count = confirmed
-        for i, s in enumerate(self.flat):
-            fn = lib.dvla_sumsq_f32 if "sh" in s else lib.dvla_sumsq_bf16
-            check(fn(s["g"].data_ptr(), s["g"].numel(), self._partial.data_ptr(), self._slots.data_ptr() + 4 * i, 0, stream),
-                  "dvla_sumsq")
-        check(lib.dvla_step_candidates(lr, float(b1), float(b2), confirmed + 1, n_cand, self._cand), "dvla_step_candidates")
-        state = self._state.data_ptr()
-        check(lib.dvla_step_verdict(self._slots.data_ptr(), len(self.flat), self._sumsq.data_ptr(), state, confirmed, n_cand,
-                                    self._cand, stream), "dvla_step_verdict")
-        ema = self.ema_decay is not None
-        if ema:     # the weights of the same candidate counts confirmed + 1 + j; the kernels pick the verdict's row
-            check(lib.dvla_ema_weights(self.ema_decay, int(self.ema_warmup), confirmed + 1, n_cand, self._ema_w), "dvla_ema_weights")
-        for bi, s in enumerate(self.flat):
-            for (lo, hi) in self._ranges(bi):
-                if hi <= lo:
-                    continue
-                if self.stochastic_rounding and "sh" not in s:
-                    self._sr_launch(lib, bi, lo, hi, None, _ONE_DOUBLE(lr), _ONE_DOUBLE(wd), b1, b2, eps, confirmed + 1, None,
-                                    max_norm, state, self._ema_w if ema else None, n_cand, stream)
-                    continue
-                if ema and "sh" in s:
-                    o = 4 * lo
-                    check(lib.dvla_adamw_f32_master_ema_guarded(
-                        s["p"].data_ptr() + o, s["g"].data_ptr() + o, s["m"].data_ptr() + o, s["v"].data_ptr() + o,
-                        s["sh"].data_ptr() + 2 * lo, s["ema"].data_ptr() + o, hi - lo, lr, float(b1), float(b2), eps, wd, max_norm,
-                        state, self._ema_w, n_cand, stream), "dvla_adamw_f32_master_ema_guarded")
-                    continue
-                if ema:
-                    o = 2 * lo
-                    check(lib.dvla_adamw_bf16_ema_guarded(
-                        s["p"].data_ptr() + o, s["g"].data_ptr() + o, s["m"].data_ptr() + o, s["v"].data_ptr() + o,
-                        s["ema"].data_ptr() + 4 * lo, hi - lo, lr, float(b1), float(b2), eps, wd, max_norm, state, self._ema_w,
-                        n_cand, stream), "dvla_adamw_bf16_ema_guarded")
-                    continue
-                if "sh" in s:
-                    o = 4 * lo
-                    check(lib.dvla_adamw_f32_master_guarded(s["p"].data_ptr() + o, s["g"].data_ptr() + o, s["m"].data_ptr() + o,
-                                                            s["v"].data_ptr() + o, s["sh"].data_ptr() + 2 * lo, hi - lo, lr,
-                                                            float(b1), float(b2), eps, wd, max_norm, state, stream),
-                          "dvla_adamw_f32_master_guarded")
-                    continue
-                o = 2 * lo
-                check(lib.dvla_adamw_bf16_guarded(s["p"].data_ptr() + o, s["g"].data_ptr() + o, s["m"].data_ptr() + o,
-                                                  s["v"].data_ptr() + o, hi - lo, lr, float(b1), float(b2), eps, wd, max_norm,
-                                                  state, stream), "dvla_adamw_bf16_guarded")
+    def _issue_readback(self):
+        """behind a guarded step's launches: the head of the device state into the next slot of the pinned ring, as a ledger ticket"""
         ticket = self._ring[self._issued % self.WINDOW]       # free: fewer than WINDOW steps are in flight after begin()
         self._issued += 1
         ticket.slot.copy_(self._state[:_lib.STEP_READBACK_BYTES], non_blocking=True)
         ticket.event.record(torch.cuda.current_stream())
         self._ledger.issued(ticket)
-        if self.master_mode:
-            self._publish_shadows_guarded()
 
     def _on_skip(self, step):
         if self._skip_warned:
@@ -463,68 +408,93 @@ class FlatAdamW(torch.optim.Optimizer):
         self._ledger.reset(applied, skipped)
         self.step_count = int(applied)
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        if self._ema_active:
-            raise RuntimeError("FlatAdamW.step() inside ema_weights(): the model holds the EMA weights, not the training weights")
-        if len(self.param_groups) > 1:
-            return self._grouped_step()
-        if self.skip_nonfinite:
-            return self._guarded_step()
-        lib = _lib.load()
-        stream = torch.cuda.current_stream().cuda_stream
-        self.step_count += 1
-        ema = self.ema_decay is not None
-        if ema:
-            check(lib.dvla_ema_weights(self.ema_decay, int(self.ema_warmup), self.step_count, 1, self._ema_w), "dvla_ema_weights")
-        grp = self.param_groups[0]
-        lr, (b1, b2), eps, wd = float(grp["lr"]), grp["betas"], float(grp["eps"]), float(grp["weight_decay"])
-        clip = self.max_grad_norm is not None
-        if clip:
+    def _norm_pass(self, lib, stream, guard, clip, per_group):
+        """The gradient's sums of squares as this step needs them -> (slots, n_slots, sumsq): what a guarded step's verdict adds
+        up (a device tensor and how many of its entries) and the address the unguarded step kernels read their clip from (None:
+        no clip, or guarded -- those kernels read the verdict's total from the state).  Global clip: dvla_sumsq_* per bucket,
+        accumulated into self._sumsq or, guarded, into one slot per bucket (without a clip as well: the verdict needs the norm).
+        clip="group": _group_norms; the groups' sums are the verdict's slots and the `_clip` kernels' table, guarded or not."""
+        if per_group:
+            self._group_norms(lib, stream, None if guard else self._sumsq.data_ptr())
+            return self._group_sumsq, len(self.param_groups), self._group_sumsq.data_ptr()
+        if guard or clip:
             for i, s in enumerate(self.flat):
                 fn = lib.dvla_sumsq_f32 if "sh" in s else lib.dvla_sumsq_bf16
-                check(fn(s["g"].data_ptr(), s["g"].numel(), self._partial.data_ptr(), self._sumsq.data_ptr(), 1 if i > 0 else 0,
-                         stream), "dvla_sumsq")
+                out, accumulate = (self._slots.data_ptr() + 4 * i, 0) if guard else (self._sumsq.data_ptr(), 1 if i > 0 else 0)
+                check(fn(s["g"].data_ptr(), s["g"].numel(), self._partial.data_ptr(), out, accumulate, stream), "dvla_sumsq")
+        if guard:
+            return self._slots, len(self.flat), None
+        return None, 0, (self._sumsq.data_ptr() if clip else None)
+
+    def _launch_range(self, lib, bi, lo, hi, hp):
+        """elements lo .. hi of bucket bi through the entry point of this step's combination (hp: what step() derived).  One
+        group: dvla_adamw_{bf16,f32_master}[_ema][_guarded]; two or more (whole buckets, with the group map):
+        dvla_adamw_{bf16,f32_master}_grouped, `_grouped_clip` with clip="group"; a bf16 bucket under stochastic rounding: _sr_launch"""
+        s = self.flat[bi]
+        master, grouped, guard, ema = "sh" in s, len(hp.lrs) > 1, hp.state is not None, hp.ema_w is not None
+        gmap = self._group_map(bi).data_ptr() if grouped else None
+        if self.stochastic_rounding and not master:
+            return self._sr_launch(lib, bi, lo, hi, gmap, hp.lrs, hp.wds, hp.b1, hp.b2, hp.eps, hp.base, hp.sumsq, hp.max_norm,
+                                   hp.state, hp.ema_w, hp.n_cand, hp.stream, per_group=hp.per_group)
+        o = (4 if master else 2) * lo       # byte offset in the parameter's dtype
+        bufs = [s[k].data_ptr() + o for k in ("p", "g", "m", "v")] + ([s["sh"].data_ptr() + 2 * lo] if master else [])
+        e = s["ema"].data_ptr() + 4 * lo if ema else None
+        name = "dvla_adamw_f32_master" if master else "dvla_adamw_bf16"
+        if grouped:
+            name += "_grouped_clip" if hp.per_group else "_grouped"
+            args = bufs + [e, hi - lo, gmap, len(hp.lrs), hp.lrs, hp.wds, hp.b1, hp.b2, hp.eps, hp.base, hp.sumsq, hp.max_norm,
+                           hp.state, hp.ema_w, hp.n_cand]
+        else:
+            name += ("_ema" if ema else "") + ("_guarded" if guard else "")
+            args = bufs + ([e] if ema else []) + [hi - lo, hp.lrs[0], hp.b1, hp.b2, hp.eps, hp.wds[0]]
+            args += [hp.max_norm, hp.state] if guard else [hp.base, hp.sumsq, hp.max_norm]
+            if ema:
+                args += [hp.ema_w, hp.n_cand] if guard else [hp.ema_w[0]]
+        check(getattr(lib, name)(*args, hp.stream), name)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        """One flow for every combination of guard, EMA, groups, stochastic rounding and clip: the norm pass, guarded the verdict
+        on the device, the EMA weights of the step counts still possible, one step launch per range (one group) or per bucket
+        (groups), guarded the readback ticket.  Every group's lr, weight_decay and max_grad_norm are read afresh."""
+        if self._ema_active:
+            raise RuntimeError("FlatAdamW.step() inside ema_weights(): the model holds the EMA weights, not the training weights")
+        lib = _lib.load()
+        stream = torch.cuda.current_stream().cuda_stream
+        groups = self.param_groups
+        n_groups, per_group = len(groups), self.clip == "group"
+        guard, ema, clip = self.skip_nonfinite, self.ema_decay is not None, self.max_grad_norm is not None
+        b1, b2, eps = common_betas_eps(groups)
+        hp = types.SimpleNamespace(
+            lrs=(ctypes.c_double * n_groups)(*[float(g["lr"]) for g in groups]),
+            wds=(ctypes.c_double * n_groups)(*[float(g["weight_decay"]) for g in groups]),
+            b1=b1, b2=b2, eps=eps, per_group=per_group, stream=stream, ema_w=self._ema_w if ema else None,
+            max_norm=self.max_grad_norm if clip else 0.0)       # guarded, <= 0: the norm only feeds the verdict
+        if per_group:   # (0: the group is not clipped; its norm still feeds the verdict and group_grad_norms())
+            hp.max_norm = (ctypes.c_float * n_groups)(*[0.0 if m is None else m for m in group_max_norms(groups, self.max_grad_norm)])
+        if guard:       # the step count is the device's: the host knows the counts still possible
+            confirmed, hp.n_cand = self._ledger.begin()
+            self.step_count = confirmed
+            hp.base, hp.state = confirmed + 1, self._state.data_ptr()
+        else:
+            self.step_count += 1
+            hp.base, hp.n_cand, hp.state = self.step_count, 1, None
+        slots, n_slots, hp.sumsq = self._norm_pass(lib, stream, guard, clip, per_group)
+        if guard:       # of the candidates the grouped kernels use what no lr enters
+            check(lib.dvla_step_candidates(hp.lrs[0], b1, b2, hp.base, hp.n_cand, self._cand), "dvla_step_candidates")
+            check(lib.dvla_step_verdict(slots.data_ptr(), n_slots, self._sumsq.data_ptr(), hp.state, confirmed, hp.n_cand,
+                                        self._cand, stream), "dvla_step_verdict")
+        if ema:         # the weights of the same candidate counts base + j; the guarded kernels pick the verdict's row
+            check(lib.dvla_ema_weights(self.ema_decay, int(self.ema_warmup), hp.base, hp.n_cand, self._ema_w), "dvla_ema_weights")
         for bi, s in enumerate(self.flat):
-            for (lo, hi) in self._ranges(bi):
-                if hi <= lo:
-                    continue
-                if self.stochastic_rounding and "sh" not in s:
-                    self._sr_launch(lib, bi, lo, hi, None, _ONE_DOUBLE(lr), _ONE_DOUBLE(wd), b1, b2, eps, self.step_count,
-                                    self._sumsq.data_ptr() if clip else None, self.max_grad_norm if clip else 0.0, None,
-                                    self._ema_w if ema else None, 1, stream)
-                    continue
-                if ema and "sh" in s:
-                    o = 4 * lo
-                    check(lib.dvla_adamw_f32_master_ema(
-                        s["p"].data_ptr() + o, s["g"].data_ptr() + o, s["m"].data_ptr() + o, s["v"].data_ptr() + o,
-                        s["sh"].data_ptr() + 2 * lo, s["ema"].data_ptr() + o, hi - lo, lr, float(b1), float(b2), eps, wd,
-                        self.step_count, self._sumsq.data_ptr() if clip else None, self.max_grad_norm if clip else 0.0,
-                        self._ema_w[0], stream), "dvla_adamw_f32_master_ema")
-                    continue
-                if ema:
-                    o = 2 * lo
-                    check(lib.dvla_adamw_bf16_ema(
-                        s["p"].data_ptr() + o, s["g"].data_ptr() + o, s["m"].data_ptr() + o, s["v"].data_ptr() + o,
-                        s["ema"].data_ptr() + 4 * lo, hi - lo, lr, float(b1), float(b2), eps, wd, self.step_count,
-                        self._sumsq.data_ptr() if clip else None, self.max_grad_norm if clip else 0.0, self._ema_w[0], stream),
-                        "dvla_adamw_bf16_ema")
-                    continue
-                if "sh" in s:
-                    o = 4 * lo      # fp32 byte offset
-                    check(lib.dvla_adamw_f32_master(s["p"].data_ptr() + o, s["g"].data_ptr() + o, s["m"].data_ptr() + o,
-                                                    s["v"].data_ptr() + o, s["sh"].data_ptr() + 2 * lo, hi - lo, lr, float(b1),
-                                                    float(b2), eps, wd, self.step_count,
-                                                    self._sumsq.data_ptr() if clip else None,
-                                                    self.max_grad_norm if clip else 0.0, stream), "dvla_adamw_f32_master")
-                    continue
-                o = 2 * lo      # bf16 byte offset
-                check(lib.dvla_adamw_bf16(s["p"].data_ptr() + o, s["g"].data_ptr() + o, s["m"].data_ptr() + o, s["v"].data_ptr() + o,
-                                          hi - lo, lr, float(b1), float(b2), eps, wd, self.step_count,
-                                          self._sumsq.data_ptr() if clip else None, self.max_grad_norm if clip else 0.0, stream),
-                      "dvla_adamw_bf16")
+            whole = [(0, s["p"].numel())] if any(self._stepped(bi)) else []
+            for lo, hi in (whole if n_groups > 1 else self._ranges(bi)):
+                if hi > lo:
+                    self._launch_range(lib, bi, lo, hi, hp)
+        if guard:
+            self._issue_readback()
         if self.master_mode:
-            self._publish_shadows()
+            self._publish_shadows_guarded() if guard else self._publish_shadows()
 
     def add_param_group(self, param_group):
         if getattr(self, "_groups_fixed", False):
@@ -544,82 +514,6 @@ class FlatAdamW(torch.optim.Optimizer):
             hit = (stepped, cpu.to(b["flat"].device))
             self._group_maps[bi] = hit
         return hit[1]
-
-    def _grouped_step(self):
-        """step() with two or more parameter groups: one dvla_adamw_*_grouped launch per bucket, guarded or not, with or without
-        the EMA; every group's lr / weight_decay is read afresh.  One clip norm over all buckets and groups -- with clip="group"
-        one per group (_group_norms instead of the dvla_sumsq_* pass, the `_clip` entry points instead of the grouped ones), every
-        group's max_grad_norm read afresh as well."""
-        lib = _lib.load()
-        stream = torch.cuda.current_stream().cuda_stream
-        b1, b2, eps = common_betas_eps(self.param_groups)
-        n_groups = len(self.param_groups)
-        lrs = (ctypes.c_double * n_groups)(*[float(g["lr"]) for g in self.param_groups])
-        wds = (ctypes.c_double * n_groups)(*[float(g["weight_decay"]) for g in self.param_groups])
-        guard, ema, clip = self.skip_nonfinite, self.ema_decay is not None, self.max_grad_norm is not None
-        max_norm = self.max_grad_norm if clip else 0.0      # guarded, <= 0: the norm only feeds the verdict
-        per_group = self.clip == "group"
-        if per_group:   # (0: the group is not clipped; its norm still feeds the verdict and group_grad_norms())
-            max_norm = (ctypes.c_float * n_groups)(*[0.0 if m is None else m
-                                                     for m in group_max_norms(self.param_groups, self.max_grad_norm)])
-        if guard:       # the verdict as in _guarded_step; of its candidates the grouped kernels use what no lr enters
-            confirmed, n_cand = self._ledger.begin()
-            self.step_count = confirmed
-            base, state, sumsq = confirmed + 1, self._state.data_ptr(), None
-            if per_group:       # the groups' sums are the verdict's slots: their total in group order, latched per group on a skip
-                self._group_norms(lib, stream, None)
-                slots, n_slots = self._group_sumsq, n_groups
-            else:
-                for i, s in enumerate(self.flat):
-                    fn = lib.dvla_sumsq_f32 if "sh" in s else lib.dvla_sumsq_bf16
-                    check(fn(s["g"].data_ptr(), s["g"].numel(), self._partial.data_ptr(), self._slots.data_ptr() + 4 * i, 0, stream),
-                          "dvla_sumsq")
-                slots, n_slots = self._slots, len(self.flat)
-            check(lib.dvla_step_candidates(lrs[0], b1, b2, base, n_cand, self._cand), "dvla_step_candidates")
-            check(lib.dvla_step_verdict(slots.data_ptr(), n_slots, self._sumsq.data_ptr(), state, confirmed, n_cand,
-                                        self._cand, stream), "dvla_step_verdict")
-        else:
-            self.step_count += 1
-            base, n_cand, state, sumsq = self.step_count, 1, None, (self._sumsq.data_ptr() if clip else None)
-            if per_group:
-                self._group_norms(lib, stream, self._sumsq.data_ptr())
-            elif clip:
-                for i, s in enumerate(self.flat):
-                    fn = lib.dvla_sumsq_f32 if "sh" in s else lib.dvla_sumsq_bf16
-                    check(fn(s["g"].data_ptr(), s["g"].numel(), self._partial.data_ptr(), self._sumsq.data_ptr(), 1 if i > 0 else 0,
-                             stream), "dvla_sumsq")
-        if per_group:
-            sumsq = self._group_sumsq.data_ptr()
-        if ema:
-            check(lib.dvla_ema_weights(self.ema_decay, int(self.ema_warmup), base, n_cand, self._ema_w), "dvla_ema_weights")
-        ema_w = self._ema_w if ema else None
-        master_fn = lib.dvla_adamw_f32_master_grouped_clip if per_group else lib.dvla_adamw_f32_master_grouped
-        bf16_fn = lib.dvla_adamw_bf16_grouped_clip if per_group else lib.dvla_adamw_bf16_grouped
-        for bi, s in enumerate(self.flat):
-            if not any(self._stepped(bi)):
-                continue
-            e = s["ema"].data_ptr() if ema else None
-            if "sh" in s:
-                check(master_fn(
-                    s["p"].data_ptr(), s["g"].data_ptr(), s["m"].data_ptr(), s["v"].data_ptr(), s["sh"].data_ptr(), e,
-                    s["p"].numel(), self._group_map(bi).data_ptr(), n_groups, lrs, wds, b1, b2, eps, base, sumsq, max_norm, state,
-                    ema_w, n_cand, stream), "dvla_adamw_f32_master_grouped")
-            elif self.stochastic_rounding:
-                self._sr_launch(lib, bi, 0, s["p"].numel(), self._group_map(bi).data_ptr(), lrs, wds, b1, b2, eps, base, sumsq,
-                                max_norm, state, ema_w, n_cand, stream, per_group=per_group)
-            else:
-                check(bf16_fn(
-                    s["p"].data_ptr(), s["g"].data_ptr(), s["m"].data_ptr(), s["v"].data_ptr(), e, s["p"].numel(),
-                    self._group_map(bi).data_ptr(), n_groups, lrs, wds, b1, b2, eps, base, sumsq, max_norm, state, ema_w, n_cand,
-                    stream), "dvla_adamw_bf16_grouped")
-        if guard:
-            ticket = self._ring[self._issued % self.WINDOW]       # free: fewer than WINDOW steps are in flight after begin()
-            self._issued += 1
-            ticket.slot.copy_(self._state[:_lib.STEP_READBACK_BYTES], non_blocking=True)
-            ticket.event.record(torch.cuda.current_stream())
-            self._ledger.issued(ticket)
-        if self.master_mode:
-            self._publish_shadows_guarded() if guard else self._publish_shadows()
 
     def _publish_shadows(self):
         """hand the freshly written bf16 copies to dreamvla_amd.ops as the shadows of the stepped masters (recorded at each
