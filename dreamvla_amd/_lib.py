@@ -237,6 +237,13 @@ SYMBOLS = {
     "dvla_adamw_bf16_sr_clip": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P, _I32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                           C.c_float, C.c_float, C.c_float, _I64, _P, C.POINTER(C.c_float), _P, C.POINTER(C.c_float),
                                           _I32, C.c_uint64, _I32, _I64, _P]),
+    "dvla_depth_range_partial_len": (C.c_int64, [_I64, _I32, _I32]),
+    "dvla_depth_colorize": (C.c_int, [_P, _P, _I64, _I32, _I32, _P, _I32, _F, _F, _I32, _I32, _I32, _P, _P]),
+    "dvla_flow_unshuffle": (C.c_int, [_P, _P, _I64, _I32, _I32, _P]),
+    "dvla_flow_wheel": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _I32, _P]),
+    "dvla_motion_mask": (C.c_int, [_P, _P, _I64, _I32, _I32, _F, _I32, _P]),
+    "dvla_motion_overlay": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _I32, _F, _F, _F, _F, _F, _F, _I32, _I32, _I32, _I32, _P]),
+    "dvla_feature_render": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _I32, _I32, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P]),
 }
 
 _lib = None

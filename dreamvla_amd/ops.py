@@ -2229,7 +2229,8 @@ def dream_render(pred, kind, current=None, patch=16):
         patch of `current`, CLIP's Normalize inverted, [0, 1] -> 0..255;
         current=None -> float32 (n, 3, H, W): the un-patchified prediction in the normalised space the head was trained in.
     kind="depth": pred (n, grid^2, patch^2) -> float32 (n, H, W), un-patchify only.
-    kind "dino" / "sam" / "traj": feature / track predictions have no picture; handed back as they are."""
+    kind "dino" / "sam" / "traj": feature / track predictions are handed back as they are; their pictures are `feature_render`,
+        `flow_unshuffle` / `flow_wheel` / `motion_mask` / `motion_overlay`, and the depth map's is `depth_colorize`."""
     if kind not in DREAM_KINDS:
         raise ValueError(f"dream_render: kind {kind!r} is not one of {DREAM_KINDS}")
     if kind not in ("image", "depth"):
@@ -2333,3 +2334,170 @@ def depth_quality(pred_f32, target_f32):
     for i, k in enumerate(("abs_rel", "rmse", "silog", "delta1")):
         out[k] = f4[:, i].reshape(lead)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# the depth, motion and feature dreams as pictures (csrc/dream_view.hip): an addition, DESIGN.md section 5 item 26
+# ---------------------------------------------------------------------------------------------------
+def _view_in(t, name, dtype, tail):
+    """a (..., *tail dims) operand of a picture kernel on the device -> (contiguous (n, *tail) view, leading shape)"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a tensor")
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
+    if t.dim() < tail:
+        raise ValueError(f"{name}: at least {tail} dimensions expected, got {tuple(t.shape)}")
+    if not t.is_cuda:
+        raise _lib.DvlaError(f"{name}: tensor is on {t.device}; the DreamVLA HIP path has no CPU fallback")
+    return t.reshape(-1, *t.shape[-tail:]).contiguous(), tuple(t.shape[:-tail])
+
+
+def _rgb(c, name):
+    c = tuple(int(v) for v in c)
+    if len(c) != 3 or any(v < 0 or v > 255 for v in c):
+        raise ValueError(f"{name}: three values in 0 .. 255 expected, got {c}")
+    return c
+
+
+def _hw(size, name):
+    h, w = (size, size) if isinstance(size, int) else tuple(size)
+    if int(h) < 1 or int(w) < 1:
+        raise ValueError(f"{name}: a positive size expected, got {size}")
+    return int(h), int(w)
+
+
+def _flow_factor(pred, name):
+    """the trajectory prediction's (grid, factor): (..., grid^2, 2 factor^2) with factor in {1, 2, 4}"""
+    L, D = pred.shape[-2], pred.shape[-1]
+    g = int(round(L ** 0.5))
+    f = {2: 1, 8: 2, 32: 4}.get(D)
+    if g * g != L or f is None:
+        raise ValueError(f"{name}: {tuple(pred.shape)} is not (..., grid^2, 2 f^2) with f in (1, 2, 4)")
+    return g, f
+
+
+def depth_colorize(depth, lo=None, hi=None, palette=None, nan_color=(0, 0, 0)):
+    """A depth map as a picture: float32 (..., h, w) -> uint8 (..., h, w, 3) = palette[index], on the device.
+    `lo`, `hi`: the range, both given (lo <= hi) or both None = per map the min / max over its finite pixels (two launches, no
+    atomics: a map's bytes do not depend on the batch around it).  In fp32, one rounding per operation, in this order:
+        s = d - lo;  r = hi - lo;  t = s / r;  t = (r > 0 and t > 0) ? min(t, 1) : 0 (hi == lo gives index 0);  index = rint(255 t)
+    A non-finite pixel gets `nan_color`.  `palette`: (256, 3) uint8 on the device; None = dream_view.depth_palette()."""
+    from .dream_view import depth_palette
+    d, lead = _view_in(depth, "depth_colorize.depth", torch.float32, 2)
+    n, h, w = d.shape
+    if h < 1 or w < 1:
+        raise ValueError(f"depth_colorize: empty maps {tuple(depth.shape)}")
+    if (lo is None) != (hi is None):
+        raise ValueError("depth_colorize: give both `lo` and `hi`, or neither (the map's own finite min / max)")
+    if lo is not None and not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+        raise ValueError(f"depth_colorize: a finite range lo <= hi expected, got ({lo}, {hi})")
+    nan_color = _rgb(nan_color, "depth_colorize.nan_color")
+    if palette is None:
+        palette = depth_palette(d.device)
+    if not isinstance(palette, torch.Tensor) or palette.dtype != torch.uint8 or tuple(palette.shape) != (256, 3):
+        raise ValueError("depth_colorize.palette: (256, 3) uint8 expected")
+    if palette.device != d.device:
+        raise _lib.DvlaError(f"depth_colorize.palette is on {palette.device}, the maps on {d.device}")
+    palette = palette.contiguous()
+    lib = _lib.load()
+    out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=d.device)
+    if n:
+        own = lo is None
+        ws = torch.empty(lib.dvla_depth_range_partial_len(n, h, w), dtype=torch.float32, device=d.device) if own else None
+        check(lib.dvla_depth_colorize(d.data_ptr(), out.data_ptr(), n, h, w, palette.data_ptr(), int(own), 0.0 if own else float(lo),
+                                      0.0 if own else float(hi), *nan_color, _ptr(ws), _stream()), "dvla_depth_colorize")
+    return out.view(*lead, h, w, 3)
+
+
+def flow_unshuffle(pred):
+    """The trajectory head's prediction as a flow field: bf16 (..., g^2, 2 f^2) with channel = c f^2 + i f + j (the
+    F.pixel_unshuffle order of losses.calvin_losses' track labels) -> float32 (..., g f, g f, 2), flow[y f + i, x f + j, c].  Exact."""
+    p, lead = _view_in(pred, "flow_unshuffle.pred", BF16, 2)
+    g, f = _flow_factor(p, "flow_unshuffle.pred")
+    n = p.shape[0]
+    out = torch.empty((n, g * f, g * f, 2), dtype=torch.float32, device=p.device)
+    if n:
+        check(_lib.load().dvla_flow_unshuffle(p.data_ptr(), out.data_ptr(), n, g * g, f, _stream()), "dvla_flow_unshuffle")
+    return out.view(*lead, g * f, g * f, 2)
+
+
+def flow_wheel(flow, size):
+    """A flow field on the reference's colour wheel (utils/visualize_utils.py): float32 (..., h, w, 2) -> uint8 (..., H, W, 3),
+    nearest-upsampled to `size` (an int or (H, W); src = dst * side_in // side_out).  With angle = atan2(dy, dx) in degrees in
+    [0, 360): Hh = trunc(angle / 2), S = 255, V = trunc(clip(32 |flow|, 0, 255)); s = Hh // 30, X = (V (30 - |Hh % 60 - 30|) + 15) // 30,
+    (R, G, B) = (V,X,0) (X,V,0) (0,V,X) (0,X,V) (X,0,V) (V,0,X) for s = 0 .. 5.  A non-finite flow is black."""
+    fl, lead = _view_in(flow, "flow_wheel.flow", torch.float32, 3)
+    n, h, w, c = fl.shape
+    if c != 2 or h < 1 or w < 1:
+        raise ValueError(f"flow_wheel: flow (..., h, w, 2) expected, got {tuple(flow.shape)}")
+    H, W = _hw(size, "flow_wheel.size")
+    out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=fl.device)
+    if n:
+        check(_lib.load().dvla_flow_wheel(fl.data_ptr(), out.data_ptr(), n, h, w, H, W, _stream()), "dvla_flow_wheel")
+    return out.view(*lead, H, W, 3)
+
+
+def motion_mask(pred, thr=1.0, dilate=False):
+    """Where the policy expects motion -- the reference's "dynamic region": the trajectory prediction bf16 (..., g^2, 2 f^2) ->
+    bool (..., g, g): the fp32 means of a token's f^2 dx and dy, mx^2 + my^2 > thr^2 (thr in flow pixels), `dilate`: OR over the
+    3 x 3 neighbourhood.  At f = 2 on the 28 x 28 flow this is losses.calvin_losses' `fmask`: avg_pool2d(2), norm > 1,
+    max_pool2d(3, 1, 1) -- dilated for the primary view, not for the wrist view."""
+    p, lead = _view_in(pred, "motion_mask.pred", BF16, 2)
+    g, f = _flow_factor(p, "motion_mask.pred")
+    thr = float(thr)
+    if not (thr >= 0.0 and math.isfinite(thr)):
+        raise ValueError(f"motion_mask: thr >= 0 expected, got {thr}")
+    n = p.shape[0]
+    out = torch.empty((n, g, g), dtype=torch.uint8, device=p.device)
+    if n:
+        check(_lib.load().dvla_motion_mask(p.data_ptr(), out.data_ptr(), n, g * g, f, thr, int(bool(dilate)), _stream()),
+              "dvla_motion_mask")
+    return out.view(torch.bool).view(*lead, g, g)
+
+
+def motion_overlay(mask, current, tint=(255, 64, 0), alpha=96):
+    """The current frame with the motion mask on it: mask bool or uint8 (..., g, g), current (..., 3, H, W) bf16 = the model's
+    CLIP-normalised input (the `current` of dream_render) -> uint8 (..., H, W, 3).  Every pixel is de-normalised exactly as
+    dream_render does (rint(255 clamp(x std + mean, 0, 1))); inside masked cells v -> (v (256 - alpha) + tint alpha + 128) >> 8.
+    H, W multiples of g, W % 4 == 0."""
+    from .preprocess import CLIP_MEAN, CLIP_STD
+    if isinstance(mask, torch.Tensor) and mask.dtype == torch.bool:
+        mask = mask.contiguous().view(torch.uint8)
+    m, lead = _view_in(mask, "motion_overlay.mask", torch.uint8, 2)
+    cur, lead_c = _view_in(current, "motion_overlay.current", BF16, 3)
+    n, g = m.shape[0], m.shape[1]
+    _, c, H, W = cur.shape
+    if m.shape[2] != g or c != 3 or cur.shape[0] != n:
+        raise ValueError(f"motion_overlay: mask (..., g, g) and current (..., 3, H, W) of one leading shape expected, got "
+                         f"{tuple(mask.shape)} and {tuple(current.shape)}")
+    tint = _rgb(tint, "motion_overlay.tint")
+    alpha = int(alpha)
+    if not 0 <= alpha <= 256:
+        raise ValueError(f"motion_overlay: alpha in 0 .. 256 expected, got {alpha}")
+    out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=cur.device)
+    if n:
+        check(_lib.load().dvla_motion_overlay(m.data_ptr(), cur.data_ptr(), out.data_ptr(), n, g, H, W, *CLIP_MEAN, *CLIP_STD, *tint,
+                                              alpha, _stream()), "dvla_motion_overlay")
+    return out.view(*lead_c, H, W, 3)
+
+
+def feature_render(feat, palette, size):
+    """Token features as a picture through a FIXED palette (dream_view.FeaturePalette, fitted once: the same colour means the same
+    feature direction at every control step): bf16 (..., g^2, D) -> uint8 (..., H, W, 3); per token p_k = sum_d x_d W[d, k] + b_k in
+    fp32, byte_k = rint(255 clamp((p_k - lo_k) / (hi_k - lo_k), 0, 1)), written to the token's block of pixels (nearest:
+    token = pixel * g // side; H, W need not divide by g).  One wave per token.  D % 8 == 0, else DvlaError."""
+    x, lead = _view_in(feat, "feature_render.feat", BF16, 2)
+    n, L, D = x.shape
+    g = int(round(L ** 0.5))
+    if g * g != L:
+        raise ValueError(f"feature_render: a square token grid expected, got {L} tokens")
+    if palette.dim != D:
+        raise ValueError(f"feature_render: the palette was fitted on {palette.dim} features, these have {D}")
+    if palette.W.device != x.device:
+        raise _lib.DvlaError(f"feature_render: the palette is on {palette.W.device}, the features on {x.device}: palette.to(device)")
+    H, W = _hw(size, "feature_render.size")
+    out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=x.device)
+    if n:
+        check(_lib.load().dvla_feature_render(x.data_ptr(), palette.W.data_ptr(), out.data_ptr(), n, L, D, H, W, *palette.b,
+                                              *palette.lo32, *palette.hi32, _stream()), "dvla_feature_render")
+    return out.view(*lead, H, W, 3)

@@ -24,6 +24,9 @@ over independent episodes) and removes the redundant work:
   * scores of the dreams (opt-in, `score_dreams=`; an addition): `horizon` steps later the predicted frame really arrives; the
     engine keeps both on the device and scores them there (csrc/dream_score.hip), next to the persistence baseline:
     `last_dream_scores`.
+  * pictures of the other dreams (opt-in, `dream_views=`; an addition): the same decode turns the depth, trajectory, DINO and SAM
+    dreams into uint8 frames (csrc/dream_view.hip: colour-mapped depth, flow wheel, motion mask and its overlay on the current
+    frame, features through a fixed palette): `last_dream_views`.
 
   * attention maps (opt-in, `attention=`; an addition): the newest-frame encode and the decode also report where the selected trunk
     rows -- by default the executed position's action queries -- look (csrc/attention_probe.hip), as further outputs of the same
@@ -85,7 +88,7 @@ class _Graphed:
 
 class RolloutEngine:
     def __init__(self, model, batch_size, history_len=None, use_graph=True, warmup_decodes=3, sample="newest", text="latched",
-                 dreams=(), score_dreams=False, horizon=3, attention=None):
+                 dreams=(), score_dreams=False, horizon=3, attention=None, dream_views=None):
         self.model = model.module if hasattr(model, "module") else model
         m = self.model
         if m.training:
@@ -119,6 +122,15 @@ class RolloutEngine:
         self.dreams = DreamVLA._check_dreams(m, dreams)
         self.dreams_all = (sample == "all")
         self.last_dreams = {}
+        # Pictures of the depth / trajectory / feature dreams (opt-in, an addition: DESIGN.md section 5 item 26).  `dream_views`:
+        # dict(depth=True | dict(lo=, hi=[, palette=, nan_color=]), traj=True | dict(thr=1.0[, tint=, alpha=]), dino=FeaturePalette,
+        # sam=FeaturePalette), every key among `dreams`.  The pictures are made by the ops.* functions from the very tensors that
+        # `last_dreams` holds, inside the same eager or captured decode, and land in `last_dream_views` (see _render_views).
+        # None: no tensors, no launches, the same graphs.
+        self.dream_views = self._check_dream_views(dream_views)
+        self.last_dream_views = {}
+        self._keep_frames = "image" in self.dreams or "traj" in self.dream_views
+        self._n_px = 224
         self.last_frames_u8 = None              # step_raw: the resized camera frames of the last step, (B, 2, n_px, n_px, 3) uint8
         self.frames = None                      # newest real frame (B, 2, 3, h, w), or the window's (B, S, 2, 3, h, w) with "all"
         # Scoring the dreams (opt-in, an addition: DESIGN.md section 5 item 18).  The image / depth head predicts the frame `horizon`
@@ -179,6 +191,39 @@ class RolloutEngine:
         self._team_in_decode = False
         self._team_seen = None
         self._team_entry = None                 # the sampler cache entry (workspace) the decode's team launch used
+
+    _VIEW_OPTIONS = {"depth": ("lo", "hi", "palette", "nan_color"), "traj": ("thr", "tint", "alpha")}
+
+    def _check_dream_views(self, views):
+        """`dream_views` -> {name: options}; the palettes go to the engine's device here, outside any capture"""
+        from .dream_view import FeaturePalette, depth_palette
+        if views is None:
+            return {}
+        if not isinstance(views, dict):
+            raise ValueError("dream_views: a dict(depth=..., traj=..., dino=..., sam=...) expected")
+        out = {}
+        for k, v in views.items():
+            if k not in ("depth", "traj", "dino", "sam"):
+                raise ValueError(f'dream_views: {k!r} is not one of "depth", "traj", "dino", "sam" (the image dream is a frame already)')
+            if k not in self.dreams:
+                raise ValueError(f"dream_views: {k!r} is not among dreams={self.dreams}")
+            if k in ("dino", "sam"):
+                if not isinstance(v, FeaturePalette):
+                    raise ValueError(f"dream_views[{k!r}]: a FeaturePalette expected (fitted once; see dream_view.FeaturePalette)")
+                out[k] = v.to(self.device)
+                continue
+            if v is True:
+                v = {}
+            if not isinstance(v, dict) or any(o not in self._VIEW_OPTIONS[k] for o in v):
+                raise ValueError(f"dream_views[{k!r}]: True or a dict with keys out of {self._VIEW_OPTIONS[k]}")
+            v = dict(v)
+            if k == "depth":
+                if (v.get("lo") is None) != (v.get("hi") is None):
+                    raise ValueError("dream_views['depth']: give both lo and hi, or neither")
+                pal = v.get("palette")
+                v["palette"] = depth_palette(self.device) if pal is None else pal.to(self.device)
+            out[k] = v
+        return out
 
     # ------------------------------------------------------------------------------------------------------------
     def reset(self, mask=None):
@@ -264,9 +309,9 @@ class RolloutEngine:
 
     # ------------------------------------------------------------------------------------------------------------
     def _decode_eager(self, tokens, noise, sel, *more):
-        """`more`: the kept camera frames (with an image dream), then the newest frame's resampler maps (with `attention`)"""
+        """`more`: the kept camera frames (with an image dream or a trajectory view), then the newest frame's resampler maps (with `attention`)"""
         more = list(more)
-        frames = more.pop(0) if "image" in self.dreams else None
+        frames = more.pop(0) if self._keep_frames else None
         res_maps = more.pop(0) if self.attention is not None else None
         am = getattr(self.model, "action_model", None)
         shared = getattr(am, "team_sampler", True) if am is not None else True
@@ -295,7 +340,8 @@ class RolloutEngine:
                 if self._team_in_decode:          # the workspace of the launch just made (DDIM or flow matching, any step count)
                     self._team_entry = getattr(am, "team_entry", None)
         maps = () if self.attention is None else self._attend(self.model.last_attention["trunk"], res_maps, sel)
-        return (out[0], out[1], *self._render(out, frames), *maps)
+        dreams = self._render(out, frames)
+        return (out[0], out[1], *dreams, *self._render_views(dreams, frames), *maps)
 
     _DREAM_SLOT = {"image": 2, "depth": 6, "traj": 7, "dino": 8, "sam": 9}       # positions in decode_tokens' 10-tuple
 
@@ -321,9 +367,54 @@ class RolloutEngine:
                 res.append(p.reshape(*lead, *mid, *p.shape[3:]))
         return res
 
+    _TRAJ_VIEW_KEYS = ("flow", "wheel", "mask", "overlay")
+
+    def _render_views(self, dreams, frames):
+        """the requested pictures of one decode, from the tensors `last_dreams` will hold (`dreams`, in the order of `self.dreams`),
+        flat, in the order of `self.dream_views` -- what `_views_dict` turns into `last_dream_views`:
+          "depth"        uint8 (B, [S,] views, [pred_num,] h, w, 3): ops.depth_colorize
+          "traj"         {"flow" float32 (.., g f, g f, 2): ops.flow_unshuffle; "wheel" uint8 (.., n, n, 3): ops.flow_wheel at the frame's
+                         size; "mask" bool (.., g, g): ops.motion_mask, dilated for view 0 (primary) and not for view 1 (wrist), as
+                         losses.calvin_losses' fmask; "overlay" uint8 (.., n, n, 3): ops.motion_overlay on the kept current frame}
+          "dino", "sam"  uint8 (.., n, n, 3): ops.feature_render through the palette given"""
+        res = []
+        n_px = self._n_px                                    # the side of the camera frames of this step
+        va = 2 if self.dreams_all else 1                     # the `views` axis of a dream
+        for name, opt in self.dream_views.items():
+            d = dreams[self.dreams.index(name)]
+            if name == "depth":
+                res.append(ops.depth_colorize(d, opt.get("lo"), opt.get("hi"), opt["palette"], opt.get("nan_color", (0, 0, 0))))
+            elif name == "traj":
+                flow = ops.flow_unshuffle(d)
+                thr = opt.get("thr", 1.0)
+                mask = torch.stack([ops.motion_mask(d.select(va, v), thr, dilate=(v == 0)) for v in range(d.shape[va])], dim=va)
+                cur = frames[(slice(None),) * va + (slice(0, d.shape[va]),)]
+                pn = mask.dim() - va - 3                     # 1 with a pred_num axis behind `views`
+                if pn:
+                    cur = cur.unsqueeze(va + 1).expand(*cur.shape[:va + 1], d.shape[va + 1], *cur.shape[va + 1:])
+                res += [flow, ops.flow_wheel(flow, n_px), mask,
+                        ops.motion_overlay(mask, cur, opt.get("tint", (255, 64, 0)), opt.get("alpha", 96))]
+            else:
+                res.append(ops.feature_render(d, opt, n_px))
+        return res
+
+    def _views_dict(self, flat):
+        out, flat = {}, list(flat)
+        for name in self.dream_views:
+            if name == "traj":
+                out[name] = dict(zip(self._TRAJ_VIEW_KEYS, flat[:4]))
+                flat = flat[4:]
+            else:
+                out[name] = flat.pop(0)
+        return out
+
+    @property
+    def _n_view_tensors(self):
+        return sum(4 if k == "traj" else 1 for k in self.dream_views)
+
     @torch.no_grad()
     def _decode(self, tokens, noise, sel):
-        args = (tokens, noise, sel) + ((self.frames,) if "image" in self.dreams else ())
+        args = (tokens, noise, sel) + ((self.frames,) if self._keep_frames else ())
         if self.attention is not None:
             args += (self._res_maps,)
         return (self._decode_g if self.use_graph else self._decode_eager)(*args)
@@ -445,8 +536,9 @@ class RolloutEngine:
     def _step(self, image_primary, image_wrist, state, text_token, noise):
         dt = self.dtype
         image_primary, image_wrist = image_primary.to(self.device, dt), image_wrist.to(self.device, dt)
+        self._n_px = int(image_primary.shape[-1])
         new_tok = self.encode_newest(image_primary, image_wrist, state.to(self.device, dt), text_token.to(self.device))
-        self._push(new_tok, torch.stack((image_primary, image_wrist), dim=1) if "image" in self.dreams else None)
+        self._push(new_tok, torch.stack((image_primary, image_wrist), dim=1) if self._keep_frames else None)
         # the wrapper conditions EVERY frame of the window on the current instruction (eval_utils_calvin.py:127-134 repeat the
         # text over the window), so the text token (slot 0 of a frame's 36) is not history: all S frames carry today's embedding
         self.tokens[:, :, 0] = self._text_emb.to(self.tokens.dtype).unsqueeze(1)
@@ -480,6 +572,9 @@ class RolloutEngine:
             action, arm, grip = self._actions(out[0], out[1], sel, bi)
         # the dreams of the decode whose action is returned (after a fallback: of the recomputed one)
         self.last_dreams = dict(zip(self.dreams, out[2:2 + len(self.dreams)]))
+        if self.dream_views:
+            first = 2 + len(self.dreams)
+            self.last_dream_views = self._views_dict(out[first:first + self._n_view_tensors])
         if self.attention is not None:
             # `last_attention` of this step (of the decode whose action was returned):
             #   "trunk"   (B, n_layers, R, L) fp32: the head-mean attention of the selected rows in the selected trunk layers

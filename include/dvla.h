@@ -795,6 +795,43 @@ int dvla_image_quality(const uint8_t* a, const uint8_t* b, int64_t n, int32_t he
 int64_t dvla_depth_quality_partial_len(int64_t n, int32_t height, int32_t width);
 int dvla_depth_quality(const float* pred, const float* target, int64_t n, int32_t height, int32_t width, int64_t* valid,
                        float* metrics4, void* partial, void* stream);
+/* (additive, ABI 9) The depth, motion and feature dreams as pictures (an addition, DESIGN.md section 5 item 26;
+ * csrc/dream_view.hip).  uint8 HWC out, no atomics, a frame's bytes do not depend on the batch.  All of them: n == 0: DVLA_OK,
+ * nothing launched; DVLA_ERR_ARG: a null pointer, n < 0, a size < 1, a colour outside 0 .. 255; DVLA_ERR_UNSUPPORTED as listed.
+ * level(v, lo, hi), shared by the depth and feature pictures, in fp32 with one rounding per operation (no FMA):
+ *   s = v - lo; r = hi - lo; t = s / r; t = (r > 0 and t > 0) ? min(t, 1) : 0 (hi == lo, a NaN quotient: 0); rint(255 * t), half to even.
+ * dvla_depth_colorize: depth (n, height, width) fp32 -> out (n, height, width, 3) = palette[level(d, lo, hi)], palette (256, 3)
+ *   uint8 on the device; a non-finite pixel gets (nan_r, nan_g, nan_b).  own_range == 0: lo <= hi, both finite (else
+ *   DVLA_ERR_ARG).  own_range != 0: lo / hi are per map the min / max over its finite pixels, two launches through `partial`
+ *   (dvla_depth_range_partial_len(n, height, width) 4-byte words, every word written before it is read).  n > 65535: unsupported.
+ * dvla_flow_unshuffle: pred (n, tokens, 2 factor^2) bf16, channel = c factor^2 + i factor + j (F.pixel_unshuffle's order, the
+ *   trajectory head's target) -> flow (n, g factor, g factor, 2) fp32, flow[y factor + i, x factor + j, c]; exact.  tokens = g^2,
+ *   factor in {1, 2, 4}, flow 8-byte aligned, else unsupported.
+ * dvla_flow_wheel: flow (n, in_h, in_w, 2) fp32, 8-byte aligned -> out (n, out_h, out_w, 3), nearest (src = dst * in / out, integer
+ *   division): angle = atan2(dy, dx) in degrees in [0, 360), Hh = trunc(angle / 2), V = trunc(min(32 |flow|, 255)), S = 255;
+ *   s = Hh / 30, X = (V (30 - |Hh % 60 - 30|) + 15) / 30, (R, G, B) = (V,X,0) (X,V,0) (0,V,X) (0,X,V) (X,0,V) (V,0,X) for s = 0 .. 5.
+ *   A non-finite flow is black.
+ * dvla_motion_mask: pred as dvla_flow_unshuffle takes it -> mask (n, g, g) uint8 in {0, 1}: mx, my = the fp32 means of the token's
+ *   factor^2 dx / dy; mx^2 + my^2 > thr^2; dilate != 0: the OR over the 3 x 3 neighbourhood inside the grid.  thr >= 0, finite.
+ * dvla_motion_overlay: current (n, 3, height, width) bf16, CLIP-normalised (dvla_dream_render's `current`), 8-byte aligned ->
+ *   out (n, height, width, 3) 4-byte aligned: v = rint(255 clamp(x std + mean, 0, 1)) as dvla_dream_render de-normalises, and in
+ *   the cells of mask (n, grid, grid) that are non-zero (v (256 - alpha) + tint alpha + 128) >> 8, 0 <= alpha <= 256.  height and
+ *   width multiples of grid, width % 4 == 0, else unsupported.
+ * dvla_feature_render: feat (n, tokens, dim) bf16, proj (dim, 3) fp32, both 16-byte aligned, dim % 8 == 0, tokens = g^2 (else
+ *   unsupported) -> out (n, out_h, out_w, 3): per token p_k = sum_d x_d proj[d, k] + b_k (fp32), byte k = level(p_k, lo_k, hi_k),
+ *   written to the pixels y, x with y g / out_h, x g / out_w (integer division) = the token. */
+int64_t dvla_depth_range_partial_len(int64_t n, int32_t height, int32_t width);
+int dvla_depth_colorize(const float* depth, uint8_t* out, int64_t n, int32_t height, int32_t width, const uint8_t* palette,
+                        int32_t own_range, float lo, float hi, int32_t nan_r, int32_t nan_g, int32_t nan_b, void* partial, void* stream);
+int dvla_flow_unshuffle(const void* pred, float* flow, int64_t n, int32_t tokens, int32_t factor, void* stream);
+int dvla_flow_wheel(const float* flow, uint8_t* out, int64_t n, int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w, void* stream);
+int dvla_motion_mask(const void* pred, uint8_t* mask, int64_t n, int32_t tokens, int32_t factor, float thr, int32_t dilate, void* stream);
+int dvla_motion_overlay(const uint8_t* mask, const void* current, uint8_t* out, int64_t n, int32_t grid, int32_t height, int32_t width,
+                        float mean_r, float mean_g, float mean_b, float std_r, float std_g, float std_b, int32_t tint_r,
+                        int32_t tint_g, int32_t tint_b, int32_t alpha, void* stream);
+int dvla_feature_render(const void* feat, const float* proj, uint8_t* out, int64_t n, int32_t tokens, int32_t dim, int32_t out_h,
+                        int32_t out_w, float b0, float b1, float b2, float lo0, float lo1, float lo2, float hi0, float hi1, float hi2,
+                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * MAE pretraining (models/vit_mae.py:129-256): random masking, the decoder's token un-shuffle and the patch-MSE loss, each
